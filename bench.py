@@ -7,15 +7,25 @@ every pixel sample traced and resolved to RGBA8 in HBM (and, for N>1 GPUs,
 the row tiles gathered over RCCL).  The scene is uploaded before timing.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+                  [--dump-outputs DIR] [--full]
       one process drives N GPUs through the library (RtRenderOptions.ndevices:
       row tiles + RCCL ncclGather to device 0)
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU; the
       launcher's rank count must equal --gpus)
 
-Rank 0 prints one JSON line.  `roofline` prices the trace kernel against the
-FP32 vector peak (the path is VALU-bound), `cpu_baseline`
-times the CPU oracle (the reference's serial-RNG semantics, 1 thread) on a
-bounded row-cyclic sample of the same frame.
+Rank 0 prints one JSON line.  A plain run does what the headline figure
+needs: set-up, W warm-up frames, one counting frame (the rays of a frame), the
+K timed frames, and the line.  --dump-outputs DIR writes the frame the last
+timed step left in HBM to DIR/frame.npy (float32; see dump_outputs).
+
+--full adds every other leg to the line: counting frames after the timed ones
+(checked identical), `roofline` (the trace kernel priced against the FP32
+vector peak -- the path is VALU-bound; see DESIGN.md -- with the HBM traffic
+and VALU figures of the hash-keyed profile), `post_move` (the frame after a
+camera move), `serial` (the RT_RNG_SERIAL legs; --no-serial skips them) and
+`cpu_baseline` (the CPU oracle -- the reference's serial-RNG semantics, 1
+thread, and all host cores -- on a bounded row-cyclic sample of the same
+frame; --no-cpu-baseline skips it).
 """
 from __future__ import annotations
 
@@ -42,6 +52,8 @@ METRIC = "Mrays/sec + frames/sec at 1920×1080 spp=64; 1/2/4/8 MI355X"
 FP32_VECTOR_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md, chip-level parameters
 HBM_PEAK_GBS = 8000.0
 ROW_BLOCK = 8  # multi-GPU: row-cyclic blocks of 8 image rows
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: everything written, in all
+DUMP_SEED = 20240229  # ... and the seed of the pixel sample of a larger frame
 
 
 # the frame trace launch's scheduling settings (RtRenderStats.launch_*)
@@ -178,9 +190,16 @@ def parse_args(argv=None):
     ap.add_argument("--accel", default="auto", choices=["auto", "brute", "bvh"])
     ap.add_argument("--no-serial", action="store_true",
                     help="skip the RT_RNG_SERIAL (reference-identical render()) legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: counting frames after "
+                         "the timed ones, roofline, post-move frame, SERIAL legs, CPU baseline")
     args = ap.parse_args(_translate_reference_args(sys.argv[1:] if argv is None else argv))
     if args.spp is not None and args.spp < 1:
         sys.exit(f"bench.py: --spp must be >= 1 (got {args.spp})")
+    if args.steps < 1:
+        sys.exit(f"bench.py: --steps must be >= 1 (got {args.steps})")
     return args
 
 
@@ -213,10 +232,30 @@ def _setup(args):
     return src, R.World(src), W, H, spp, depth, accel
 
 
-def _timed(args, step, stream, sync, barrier):
+def dump_outputs(dirname, frame, W, rows):
+    """--dump-outputs: what a caller of the timed path receives, the RGBA8
+    frame (`rows` image rows of W pixels) the last timed step left in `frame`,
+    as DIR/frame.npy: float32 [rows, W, 4], values 0..255.  A frame over
+    DUMP_MAX_BYTES in that form (C3's 3840x2160) is written as a fixed, seeded
+    sample of its pixels, float32 [n, 4] in ascending pixel order; scene,
+    camera and RNG are deterministic, so the same arguments give the same
+    file from run to run."""
+    img = frame[:rows * W * 4].cpu().numpy().reshape(rows * W, 4)
+    keep = DUMP_MAX_BYTES // 16  # four float32 channels per pixel
+    if img.shape[0] > keep:
+        pick = np.random.default_rng(DUMP_SEED).choice(img.shape[0], size=keep, replace=False)
+        out = img[np.sort(pick)].astype(np.float32)
+    else:
+        out = img.astype(np.float32).reshape(rows, W, 4)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "frame.npy"), out)
+
+
+def _timed(args, step, stream, sync, barrier, dump=None):
     """W warmup frames, one counting frame, then K timed frames between
     barrier + synchronize on both sides (HIP events around each frame's render
-    on the launch stream), then counting frames like the timed ones."""
+    on the launch stream), then `dump` (the last timed frame written out) and,
+    under --full, counting frames like the timed ones."""
     for _ in range(args.warmup):
         step(False)
     st_warm = step(True)  # counters of one frame (the frame is identical every step)
@@ -230,8 +269,13 @@ def _timed(args, step, stream, sync, barrier):
     sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    stats = [step(True) for _ in range(max(1, min(args.steps, 3)))]
-    assert all(s["rays"] == st_warm["rays"] for s in stats), "frames must be identical"
+    if dump is not None:
+        dump()
+    if args.full:
+        stats = [step(True) for _ in range(max(1, min(args.steps, 3)))]
+        assert all(s["rays"] == st_warm["rays"] for s in stats), "frames must be identical"
+    else:
+        stats = [st_warm]
     # (a timed frame's render is its trace launch(es): each launch zeroes the
     # other job-counter set for the next one, so no fill launch per frame)
     trace_ms = (sum(a.elapsed_time(b) for a, b in evs) / args.steps
@@ -363,16 +407,19 @@ def single_process(args):
         for d in range(ngpu):
             torch.cuda.synchronize(d)
 
-    st_warm, st0, elapsed, trace_ms, count_trace_ms = _timed(args, step, stream, sync, lambda: None)
-    moved = _post_move(world, step, sync)
+    dump = (lambda: dump_outputs(args.dump_outputs, frame, W, H)) if args.dump_outputs else None
+    st_warm, st0, elapsed, trace_ms, count_trace_ms = _timed(args, step, stream, sync, lambda: None,
+                                                             dump)
     rows = R.tile_rows(H, ROW_BLOCK, 0, ngpu) if ngpu > 1 else H
     if ngpu > 1:
         par = (f"row-tiles x{ngpu} (block {ROW_BLOCK}), one process, RCCL ncclGather "
                f"({ranks} ranks) to device 0 + assemble kernel")
     else:
         par = "one device renders the frame in place (no RCCL call)"
-    extra = {"rccl_ranks": ranks, "launch": "single process", "post_move": moved}
-    if ngpu == 1 and not args.no_serial:
+    extra = {"rccl_ranks": ranks, "launch": "single process"}
+    if args.full:
+        extra["post_move"] = _post_move(world, step, sync)
+    if args.full and ngpu == 1 and not args.no_serial:
         torch.cuda.set_stream(torch.cuda.default_stream(dev))
         extra["serial"] = serial_legs()
     _report(args, src, world, W, H, spp, depth, st0, st_warm["rays"] * args.steps, elapsed,
@@ -436,8 +483,12 @@ def multi_process(args, world_size):
         return st
 
     barrier = dist.barrier if nr > 1 else (lambda: None)
+    dump = None
+    if args.dump_outputs and rank == 0:  # rank 0 holds the assembled frame (its tile when alone)
+        def dump():
+            dump_outputs(args.dump_outputs, tile if frame is None else frame, W, H)
     st_warm, st0, elapsed, trace_ms, count_trace_ms = _timed(
-        args, step, stream, torch.cuda.synchronize, barrier)
+        args, step, stream, torch.cuda.synchronize, barrier, dump)
     rays = st_warm["rays"] * args.steps
     if nr > 1:
         tdev = dev if backend == "nccl" else torch.device("cpu")
@@ -467,8 +518,10 @@ def multi_process(args, world_size):
         dist.destroy_process_group()
 
 
-def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, count_trace_ms,
-            nr, rows, parallelism, extra):
+def _roofline(args, W, st0, trace_ms, count_trace_ms, rows, launch):
+    """--full: the `roofline` entry of the line (no GPU work: the counters of a
+    counting frame priced over the timed frames' HIP-event time, beside the
+    figures of the committed profile of the same trace kernel)."""
     launches = max(1, st0["trace_launches"])
     flops_per_launch = executed_flops(st0) / launches
     achieved_tflops = flops_per_launch / (trace_ms * 1e-3) / 1e12
@@ -480,9 +533,8 @@ def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, co
     # machine code (tools/kernel_hash.py) -- the code those counters describe --
     # next to the same hash of the library this run loaded; the whole-.so
     # hashes are reported too
-    # the timed (uncounted) kernel's schedule: profiles record it with their
-    # counters, and the traffic below counts only if it is the same
-    launch = {k[len("launch_"):]: st0[k] for k in LAUNCH_KEYS}
+    # `launch` is the timed (uncounted) kernel's schedule: profiles record it
+    # with their counters, and the traffic below counts only if it is the same
     traffic, tsrc, ent = None, None, {}
     tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
     if os.path.exists(tfile):
@@ -503,7 +555,6 @@ def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, co
                 "same_launch_settings": ent.get("launch") == launch,
                 "profiled_lib_sha256": ent.get("lib_sha256"), "benched_lib_sha256": loaded,
                 "same_binary": ent.get("lib_sha256") == loaded}
-    ms_per_step = elapsed / args.steps * 1e3
     # VALU evidence of the same hash-keyed profile (tools/pmc_summary.py): lanes
     # active per VALU instruction, VALU lane-slots per ray and the issue rate
     # against the v_add_f32 issue rate measured on the box
@@ -533,6 +584,25 @@ def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, co
             # SURVEY 8(d) literally: no price for box tests
             "s8d_literal_tflops": s8d_tflops,
             "s8d_literal_frac": s8d_tflops / FP32_VECTOR_PEAK_TFLOPS}
+    return {"bound": "valu", "achieved": achieved_tflops,
+            "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved_tflops / FP32_VECTOR_PEAK_TFLOPS, "traffic": traffic,
+            "traffic_source": tsrc,
+            "kernel": "trace_kernel", "avg_launch_ms": trace_ms,
+            "counting_variant_ms": count_trace_ms,
+            "flops_per_launch": flops_per_launch, "flops": "executed work",
+            "brute_force_equivalent_tflops": alg_tflops,
+            "algorithmic_hbm_gbs": out_bytes / (trace_ms * 1e-3) / 1e9,
+            "hbm_peak_gbs": HBM_PEAK_GBS, **valu}
+
+
+def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, count_trace_ms,
+            nr, rows, parallelism, extra):
+    """The result line.  A plain run reports the timing and the counters of its
+    one counting frame; --full adds `roofline` and, on one GPU, `cpu_baseline`
+    (and the callers' `post_move` / `serial` legs in `extra`)."""
+    launch = {k[len("launch_"):]: st0[k] for k in LAUNCH_KEYS}
+    ms_per_step = elapsed / args.steps * 1e3
     result = {
         "metric": METRIC,
         "value": rays / elapsed / 1e6,
@@ -552,16 +622,8 @@ def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, co
                                f"{world.num_spheres} spheres, {world.num_triangles} triangles, "
                                "COUNTER RNG", "width": W, "height": H, "spp": spp,
                    "depth": depth, "parallelism": parallelism},
-        "roofline": {"bound": "valu", "achieved": achieved_tflops,
-                     "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved_tflops / FP32_VECTOR_PEAK_TFLOPS, "traffic": traffic,
-                     "traffic_source": tsrc,
-                     "kernel": "trace_kernel", "avg_launch_ms": trace_ms,
-                     "counting_variant_ms": count_trace_ms,
-                     "flops_per_launch": flops_per_launch, "flops": "executed work",
-                     "brute_force_equivalent_tflops": alg_tflops,
-                     "algorithmic_hbm_gbs": out_bytes / (trace_ms * 1e-3) / 1e9,
-                     "hbm_peak_gbs": HBM_PEAK_GBS, **valu},
+        **({"roofline": _roofline(args, W, st0, trace_ms, count_trace_ms, rows, launch)}
+           if args.full else {}),
         "launch_settings": launch,
         "rays_per_frame": st0["rays"],
         "accel": {1: "brute", 2: "bvh"}.get(st0["accel"], "?"),
@@ -573,7 +635,7 @@ def _report(args, src, world, W, H, spp, depth, st0, rays, elapsed, trace_ms, co
                     "brute_force_sphere_tests": st0["sphere_tests"] / st0["rays"]},
     }
     result.update(extra)
-    if nr == 1 and not args.no_cpu_baseline:
+    if args.full and nr == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(src, W, H, spp, depth, args.cpu_seconds)
     print(json.dumps(result))
 

@@ -69,6 +69,46 @@ def test_spp_and_depth_override_the_config():
     assert (spp, depth) == (32, 3)
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    b = _bench_module()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = b.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    r = _run(["--steps", "0"], {})
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the RGBA8 frame as float32 [rows, W, 4]; a frame over the
+    byte budget as the same seeded pixel sample on every call, within the budget."""
+    import numpy as np
+    import torch
+
+    b = _bench_module()
+    w, h = 37, 11
+    px = np.random.default_rng(5).integers(0, 256, h * w * 4, dtype=np.uint8)
+    frame = torch.from_numpy(np.concatenate([px, np.zeros(64, np.uint8)]))  # (a longer buffer)
+    b.dump_outputs(str(tmp_path / "a"), frame, w, h)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (h, w, 4)
+    assert np.array_equal(got, px.reshape(h, w, 4).astype(np.float32))
+    assert b.DUMP_MAX_BYTES == 64 << 20
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 100 * 16)
+    b.dump_outputs(str(tmp_path / "b"), frame, w, h)
+    b.dump_outputs(str(tmp_path / "c"), frame, w, h)
+    s1, s2 = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "c" / "frame.npy")
+    assert s1.dtype == np.float32 and s1.shape == (100, 4) and s1.nbytes <= 100 * 16
+    assert np.array_equal(s1, s2)
+    # every sampled pixel is a pixel of the frame, in ascending pixel order
+    rows = px.reshape(h * w, 4).astype(np.float32)
+    pos = 0
+    for p in s1:
+        while not np.array_equal(rows[pos], p):
+            pos += 1
+        pos += 1
+
+
 def test_bad_spp_and_reference_args_are_refused():
     r = _run(["--spp", "0"], {})
     assert r.returncode != 0 and "--spp must be >= 1" in r.stderr

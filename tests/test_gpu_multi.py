@@ -103,12 +103,43 @@ def _bench_env():
 
 def test_bench_single_process_gpus_1():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config",
-                        "c1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                        "c1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        env=_bench_env(), capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["launch"] == "single process"
     assert line["value"] > 0 and line["rays_per_frame"] > 65536
+    # --full: the legs beside the headline figure (the CPU baseline switched off)
+    assert len(line["serial"]) == 3 and line["roofline"]["avg_launch_ms"] > 0
+    assert "post_move" in line and "cpu_baseline" not in line
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_frame(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times N steps and
+    prints the headline line without the --full legs; --dump-outputs writes
+    the frame of the last timed step, which is the frame of the same settings
+    through rt_render_ex, bit for bit."""
+    import scenes as S
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config",
+                        "c1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=_bench_env(), capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    # value = rays of the timed frames per second of them
+    assert line["value"] == pytest.approx(line["rays_per_frame"] / line["ms_per_step"] / 1e3, rel=1e-9)
+    for leg in ("serial", "cpu_baseline", "roofline", "post_move"):
+        assert leg not in line, leg
+    assert sorted(os.listdir(out)) == ["frame.npy"]
+    frame = np.load(out / "frame.npy")
+    make_scene, w, h, spp, depth = S.CONFIGS["c1"]
+    assert frame.dtype == np.float32 and frame.shape == (h, w, 4)
+    ref, _ = R.World(make_scene()).render(w, h, spp, depth)
+    assert np.array_equal(frame, ref.astype(np.float32))
 
 
 def test_bench_torchrun_two_ranks_rehearsal():

@@ -14,4 +14,4 @@ step() {  # step <name> <seconds> <cmd...>: rc 0/1 continue, anything else stops
 [ -x tools/ubench_valu ] && step ubench 120 ./tools/ubench_valu
 step smoke 400 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 1200 python -m pytest tests -q -m gpu -x
-step bench 600 python bench.py --steps 3 --warmup 1
+step bench 600 python bench.py --full --steps 3 --warmup 1

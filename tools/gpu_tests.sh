@@ -14,4 +14,4 @@ step() {  # step <name> <seconds> <cmd...>: rc 0/1 continue, anything else stops
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ${PYTEST_ARGS}
-[ -n "$NO_BENCH" ] || step bench 600 python bench.py --steps 5 --warmup 2
+[ -n "$NO_BENCH" ] || step bench 600 python bench.py --full --steps 5 --warmup 2

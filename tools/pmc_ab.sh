@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for v in "fused:RT_AMD_FUSED=1" "p4:RT_AMD_RESOLVE_PIX=4" "slab:RT_AMD_FUSED=0"; do
   name=${v%%:*}; kv=${v#*:}
-  env "$kv" timeout -k 10 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_REQ_sum -d "$OUT/$name" -o "$name" --output-format csv -- python3 "$REPO/bench.py" --no-cpu-baseline --steps 2 --warmup 1 > "$OUT/$name.log" 2>&1 || exit 1
+  env "$kv" timeout -k 10 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_REQ_sum -d "$OUT/$name" -o "$name" --output-format csv -- python3 "$REPO/bench.py" --full --no-cpu-baseline --steps 2 --warmup 1 > "$OUT/$name.log" 2>&1 || exit 1
   python3 - "$OUT/$name" "$name" <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + "/*counter_collection.csv")[0]

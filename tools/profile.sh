@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # run <name> <secs> <rocprof args...>
     local name=$1 secs=$2; shift 2
     timeout -k 10 "$secs" rocprofv3 "$@" -d "$OUT/$name" -o "$name" --output-format csv \
-        -- python3 "$REPO/bench.py" --no-cpu-baseline --no-serial "${BENCH_ARGS[@]}" > "$OUT/$name.log" 2>&1
+        -- python3 "$REPO/bench.py" --full --no-cpu-baseline --no-serial "${BENCH_ARGS[@]}" > "$OUT/$name.log" 2>&1
     local rc=$?
     echo "$name rc=$rc"; tail -2 "$OUT/$name.log"
     [ $rc -eq 0 ] || exit $rc
