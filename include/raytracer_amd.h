@@ -127,6 +127,13 @@ typedef struct RtRenderStats {
   uint32_t launch_wsteps;
   uint32_t launch_block_threads;
   uint32_t launch_blocks;
+  /* Where that launch's sphere walk read the tree from: 0 no tree (brute
+   * force), 1 global memory, 2 the workgroup's LDS copy as 64-B box records,
+   * 3 the LDS copy as 128-B octant corner records (sphere-only scenes whose
+   * image fits; RT_AMD_CORNER=0 keeps the box records) -- and the LDS bytes
+   * that copy takes per workgroup (0 without one). */
+  uint32_t sphere_tree;
+  uint32_t sphere_tree_lds_bytes;
 } RtRenderStats;
 
 /* spp 16, depth 8 (lib.rs:51), SERIAL, seed 2547549, one rank, device -1,

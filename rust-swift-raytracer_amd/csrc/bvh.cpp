@@ -958,7 +958,31 @@ SphereBVH build_sphere_bvh(const std::vector<Sphere> &spheres, uint32_t leaf_siz
         out.prims[i * 4 + 3] = s.radius * s.radius;  // same bits as the brute-force table
         out.prim_id[i] = prims[i].id;
     }
+    build_corner_image(out);
     return out;
+}
+
+void build_corner_image(SphereBVH &bv) {
+    bv.corner.clear();
+    const size_t nn = bv.nodes.size() / 8;
+    if (nn == 0 || nn > kCornerMaxNodes || bv.prim_id.size() > kCornerMaxPrims) return;
+    auto fbits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+    std::vector<uint32_t> img(nn * 32);
+    for (size_t n = 0; n < nn; ++n) {
+        const float *b = &bv.nodes[n * 8];
+        const uint32_t a = fbits(b[3]), w = fbits(b[7]);  // (bvh.h: child | leaf bit, axis | count)
+        const bool leaf = (a & kLeafBit) != 0;
+        if (leaf && ((a & ~kLeafBit) >= kCornerMaxPrims || w > 7u)) return;
+        for (uint32_t o = 0; o < 8; ++o) {
+            uint32_t *s = &img[n * 32 + o * 4];
+            for (int k = 0; k < 3; ++k) s[k] = fbits(((o >> k) & 1u) ? b[4 + k] : b[k]);
+            const uint32_t m = bv.miss[n * 8 + o];
+            const uint32_t miss = m == kNodeEnd ? kCornerEnd : m;
+            const uint32_t next = leaf ? kCornerLeaf | (a & ~kLeafBit) << 3 | w : a + ((o >> w) & 1u);
+            s[3] = miss | next << 16;
+        }
+    }
+    bv.corner = std::move(img);
 }
 
 }  // namespace rtamd

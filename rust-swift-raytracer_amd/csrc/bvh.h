@@ -37,7 +37,23 @@ struct SphereBVH {
     float centre[3] = {0, 0, 0};
     float radius = 0, rmax = 0, mag = 0, inv_rmin = 0;
     uint32_t depth = 0;
+    // Corner records (render.hip stage_tree copies them to LDS verbatim): 32 u32
+    // per node, 8 slots of 4, one per ray-direction octant o (bit k set: the
+    // direction is negative on axis k).  Slot o = the box's near corner for o
+    // (per axis lo where the direction is positive, hi where it is negative;
+    // the far corner of o is the near corner of 7 - o) and o's link word
+    //   miss(o) | next(o) << 16      inner node: next = the near child
+    //   miss(o) | (kCornerLeaf | first << 3 | count) << 16      leaf
+    // with u16 node indices, kCornerEnd = the end of the walk.  The leaf flag is
+    // the word's sign bit; a leaf's next node is its miss link.  Empty when the
+    // tree does not fit the encoding (kCornerMaxNodes nodes, kCornerMaxPrims
+    // spheres, 7 per leaf).
+    std::vector<uint32_t> corner;
 };
+constexpr uint32_t kCornerLeaf = 0x8000u, kCornerEnd = 0xFFFFu;
+constexpr uint32_t kCornerMaxNodes = 0x7FFFu, kCornerMaxPrims = 0x1000u;
+// Fills bv.corner from bv.nodes / bv.miss (build_sphere_bvh calls it).
+void build_corner_image(SphereBVH &bv);
 
 SphereBVH build_sphere_bvh(const std::vector<Sphere> &spheres, uint32_t leaf_size);
 

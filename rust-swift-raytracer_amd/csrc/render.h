@@ -204,7 +204,11 @@ RT_HOST_DEVICE inline uint32_t serial_lo(const SerialPred &M, uint32_t a, uint32
     return (uint32_t)c;
 }
 
-hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream);
+// corner (sphere-only frames with p.use_lds): the corner records (bvh.h
+// SphereBVH::corner, 8 uint4 per node) the workgroups stage instead of the box
+// records (the corner-record kernel instances; trace_corner_lds bytes each)
+hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream,
+                        const uint4 *corner = nullptr);
 // Primary sphere lists built on the device (bvh.h build_primary_sphere_lists,
 // the same double arithmetic per sphere, then one thread per pixel collecting
 // the spheres whose projected box covers it, in tree order): rec gets 2 u32
@@ -340,7 +344,8 @@ hipError_t launch_resolve_ex(const float *samples, uint32_t *out, uint32_t npix,
 hipError_t launch_assemble(const uint32_t *gathered, uint32_t *out, uint32_t width, uint32_t height,
                            uint32_t row_block, uint32_t nranks, uint32_t max_rows,
                            hipStream_t stream);
-// variant: 0 brute force, 1 BVH from global memory, 2 BVH staged in LDS;
+// variant: 0 brute force, 1 BVH from global memory, 2 BVH staged in LDS, 3 the
+// corner-record instances (mesh 0, kinds 0 and 1);
 // step: the sliced-walk kernel (TraceParams::step); mesh: trace_mesh_kind
 // workgroups per CU of one trace_kernel instance (kind: 0 the lean frame
 // kernel, 1 the counting frame kernel, 2 the SERIAL passes)
@@ -351,11 +356,23 @@ hipError_t trace_occupancy(int *blocks_per_cu, int variant, size_t lds_bytes, bo
 inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : tree ? 2 : 1; }
 // kMesh 3: kind 2 walked through the 4-wide image (TraceParams::tw_nodes); the
 // SERIAL passes keep the binary walk
-size_t trace_lds_bytes(const TraceParams &p);
+size_t trace_lds_bytes(const TraceParams &p, bool corner = false);
 // the sphere tree's LDS copy (render.hip stage_tree)
 __host__ __device__ inline size_t trace_tree_lds(uint32_t nnodes, uint32_t nprims, uint32_t nsph_padded) {
     return (size_t)nnodes * 64 + (size_t)nprims * 20 + (size_t)nsph_padded * 36;
 }
+// the corner-record copy: 128-B node records, prims and ids (shading records
+// and kinds stay in global memory)
+__host__ __device__ inline size_t trace_corner_lds(uint32_t nnodes, uint32_t nprims) {
+    return (size_t)nnodes * 128 + (size_t)nprims * 20;
+}
+// LDS of one CU, shared by its resident workgroups; a kernel takes more than
+// kLdsDefaultMax per workgroup only after trace_lds_opt_in
+constexpr size_t kLdsPerCu = 160 * 1024, kLdsDefaultMax = 64 * 1024;
+// Lets every LDS-tree trace_kernel instance take up to kLdsPerCu of dynamic
+// LDS (hipFuncAttributeMaxDynamicSharedMemorySize), once per device, before
+// the occupancy queries and the launches.
+hipError_t trace_lds_opt_in();
 // the LDS copy addresses its 64-B node records with u16 byte addresses (0xFFFF: end)
 constexpr uint32_t kLdsTreeMaxNodes = 1023;
 // threads per trace workgroup: LDS-tree kernels (per kernel family, trace_mesh_kind
@@ -363,6 +380,6 @@ constexpr uint32_t kLdsTreeMaxNodes = 1023;
 uint32_t trace_block_threads(bool lds, int mesh, int kind);
 // dynamic LDS of one trace workgroup: the sphere tree (lds) and, for the wide
 // triangle walk, every lane's stack (u16 entries)
-size_t trace_dyn_lds(const TraceParams &p, bool lds, bool wide, uint32_t threads);
+size_t trace_dyn_lds(const TraceParams &p, bool lds, bool wide, uint32_t threads, bool corner = false);
 
 }  // namespace rtamd

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "exactdiv.h"
 #include "render.h"
@@ -246,13 +247,14 @@ constexpr float kErrK = 3.0e-3f;  // >= 2.7x the derived sqrt(30u) = 1.12e-3 (DE
 // Where the traversal reads the tree from: global memory (any size) or the
 // workgroup's LDS copy (staged once per persistent workgroup).
 struct BvhView {
-    const float4 *nodes;     // global: 2 per node; LDS: 64-B records (box | 8 x u32 link pairs)
+    const float4 *nodes;     // global: 2 per node; LDS: 64-B records (box | 8 x u32 link pairs),
+                             // or 128-B corner records (8 x (near corner | link pair); corner::trace_kernel)
     const uint32_t *miss32;  // global: 8 x u32 per node
     const uint16_t *miss16;  // (unused: the LDS links live in the node records)
     const float4 *prims;
     const uint32_t *ids;
-    const float4 *shade;     // per-sphere shading records (2 x float4)
-    const uint32_t *kinds;
+    const float4 *shade;     // per-sphere shading records (2 x float4): LDS, or (global walk, corner records)
+    const uint32_t *kinds;   // p.sph_shade / p.sph_kind in global memory
 };
 
 // Spheres through the exact-pruning BVH (bvh.h): big spheres first (brute
@@ -364,6 +366,71 @@ __device__ __forceinline__ bool sphere_node(const BvhView &v, F3 inv, uint32_t o
     // read when it is set)
     leaf = ((a & ~kLeafBitDev) << 3) | __float_as_uint(B1.w);
     return !skip && is_leaf;
+}
+
+// One node of the corner-record LDS tree (bvh.h SphereBVH::corner): the same
+// test as sphere_node from two reads, the ray octant's near corner with its
+// link word and the far corner (the near corner of octant 7 - o).  `node` is a
+// node index; offn / offf = the LDS base plus the two slots' offsets in a
+// record (16 o and 16 (7 - o)); nn / nf = the near and far faces' slab offsets
+// (sphere_corner_slabs).  Picking the near face by the sign of inv instead of
+// min / max gives the same tn and tf bit for bit: per axis the far value
+// exceeds the near one (DESIGN.md 5.2 point 4), so min and max would pick the
+// same two values.  v_max3 / v_min3 drop a NaN operand like fminf / fmaxf do
+// and give NaN when all three are, which no compare below takes for a skip.
+__device__ __forceinline__ bool sphere_node_corner(uint32_t offn, uint32_t offf, F3 inv, float best_t, F3 nn,
+                                                   F3 nf, uint32_t &node, uint32_t &leaf, uint32_t &node_tests) {
+    ++node_tests;
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float f3v __attribute__((ext_vector_type(3)));
+    // (node << 7) + offset as one v_lshl_add_u32 per read: the compiler shares
+    // the shift between the two addresses instead, three instructions
+    uint32_t an, af;
+    asm("v_lshl_add_u32 %0, %1, 7, %2" : "=v"(an) : "v"(node), "v"(offn));
+    asm("v_lshl_add_u32 %0, %1, 7, %2" : "=v"(af) : "v"(node), "v"(offf));
+    const float4 N = *(const __attribute__((address_space(3))) float4 *)(uintptr_t)an;
+    const f3v Fc = *(const __attribute__((address_space(3))) f3v *)(uintptr_t)af;
+    const float tnx = __builtin_fmaf(N.x, inv.x, nn.x), tfx = __builtin_fmaf(Fc.x, inv.x, nf.x);
+    const float tny = __builtin_fmaf(N.y, inv.y, nn.y), tfy = __builtin_fmaf(Fc.y, inv.y, nf.y);
+    const float tnz = __builtin_fmaf(N.z, inv.z, nn.z), tfz = __builtin_fmaf(Fc.z, inv.z, nf.z);
+    const float tn = fmaxf(fmaxf(tnx, tny), tnz);
+    const float tf = fminf(fminf(tfx, tfy), tfz);
+    // (the three skip conditions of sphere_node)
+    const bool skip = tn > tf || tf < 0.001f || __float_as_int(tn) > __float_as_int(best_t);
+    // link word: miss | next << 16, a leaf's upper half = kCornerLeaf | leaf word
+    // (the sign bit), its next node the miss link
+    const uint32_t lw = __float_as_uint(N.w);
+    const bool is_leaf = (int32_t)lw < 0;
+    node = (skip || is_leaf) ? (lw & 0xFFFFu) : (lw >> 16);
+    leaf = (lw >> 16) & 0x7FFFu;
+    return !skip && is_leaf;
+#else
+    (void)offn; (void)offf; (void)inv; (void)best_t; (void)nn; (void)nf;
+    node = 0xFFFFu;
+    leaf = 0;
+    return false;
+#endif
+}
+
+// The corner walk's first node (an index): the root's near child for the
+// ray's octant, as sphere_walk_entry.  lbase: the image's LDS address.
+__device__ __forceinline__ uint32_t sphere_corner_entry(uint32_t lbase, uint32_t oct, uint32_t nnodes) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (nnodes > 1u)
+        return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)(lbase + 16u * oct + 12u) >> 16;
+#endif
+    (void)lbase; (void)oct; (void)nnodes;
+    return 0;
+}
+
+// The corner walk's slab offsets: sphere_slabs' values, sorted per axis by the
+// ray's octant.  The near face is lo where the direction is positive (offset
+// -((o + e) inv), sphere_slabs' nlo) and hi where it is negative (-((o - e)
+// inv), its nhi); the far face takes the other one.
+__device__ __forceinline__ void sphere_corner_slabs(F3 org, F3 inv, float e, uint32_t oct, F3 &nn, F3 &nf) {
+    const float ex = (oct & 1u) ? -e : e, ey = (oct & 2u) ? -e : e, ez = (oct & 4u) ? -e : e;
+    nn = f3(-((org.x + ex) * inv.x), -((org.y + ey) * inv.y), -((org.z + ez) * inv.z));
+    nf = f3(-((org.x - ex) * inv.x), -((org.y - ey) * inv.y), -((org.z - ez) * inv.z));
 }
 
 // The walk's first node.  With the LDS tree the root's own box test is
@@ -845,8 +912,14 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
 // Node references are record LDS addresses (base + index * 64; the kernels
 // have no static LDS before it, so base is 0 and they stay below 0xFFFF: the
 // copy holds <= kLdsTreeMaxNodes nodes); 0xFFFF stays the end marker.
-template <bool kLds>
-__device__ __forceinline__ uint32_t stage_tree(const TraceParams &p, float4 *lds, BvhView &view) {
+// Corner layout (kCorner instances: sphere-only frame kernels): corner records
+// (128 B, bvh.h SphereBVH::corner, `corner`, copied verbatim: their links are
+// node indices) | prims (float4) | ids (u32).  The shading records and kinds
+// are not staged: view.shade / view.kinds point at p.sph_shade / p.sph_kind.
+// Returns the image's LDS address.
+template <bool kLds, bool kCorner>
+__device__ __forceinline__ uint32_t stage_tree(const TraceParams &p, const uint4 *corner, float4 *lds,
+                                               BvhView &view) {
     if (!kLds) {
         view = BvhView{p.bvh_nodes, p.bvh_miss, nullptr, p.bvh_prims, p.bvh_prim_id,
                        p.sph_shade, p.sph_kind};
@@ -854,6 +927,19 @@ __device__ __forceinline__ uint32_t stage_tree(const TraceParams &p, float4 *lds
     }
     float4 *n4 = lds;
     const uint32_t lbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4 *)lds;
+    if (kCorner) {
+        float4 *c4 = n4 + 8u * p.nnodes;
+        uint32_t *cid = reinterpret_cast<uint32_t *>(c4 + p.nprims);
+        const float4 *g = reinterpret_cast<const float4 *>(corner);
+        for (uint32_t i = threadIdx.x; i < 8u * p.nnodes; i += blockDim.x) n4[i] = g[i];
+        for (uint32_t i = threadIdx.x; i < p.nprims; i += blockDim.x) {
+            c4[i] = p.bvh_prims[i];
+            cid[i] = p.bvh_prim_id[i];
+        }
+        __syncthreads();
+        view = BvhView{n4, nullptr, nullptr, c4, cid, p.sph_shade, p.sph_kind};
+        return lbase;
+    }
     float4 *p4 = n4 + 4 * p.nnodes;
     float4 *s4 = p4 + p.nprims;
     uint32_t *id = reinterpret_cast<uint32_t *>(s4 + 2 * p.nsph_padded);
@@ -967,10 +1053,10 @@ constexpr int trace_waves_per_eu(bool lds, int mesh, int kind) {
     return kind != 0 ? RT_WAVES_PER_EU : mesh == 3 ? RT_WAVES_PER_EU_WIDE : mesh ? RT_WAVES_PER_EU_MESH
                        : lds ? RT_WAVES_PER_EU_SPHERES : RT_WAVES_PER_EU_SPHERES_GLOBAL;
 }
-template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial = false>
-__global__ __launch_bounds__(trace_threads(kLds, kMesh, kSerial ? 2 : kCount ? 1 : 0))
-__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, kSerial ? 2 : kCount ? 1 : 0), 8)))
-void trace_kernel(TraceParams p) {
+// kCorner: the LDS tree is the corner-record image `corner` (sphere-only frame
+// kernels, corner::trace_kernel below); every other instance is trace_kernel.
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner>
+__device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
     // SERIAL count passes: the walk of the previous pass set the first sample
     // and this iteration's candidates per sample (ctrl[5], <= the launch's K)
     if (kSerial && p.ctrl != nullptr) {
@@ -1028,7 +1114,7 @@ void trace_kernel(TraceParams p) {
     };
     extern __shared__ float4 lds[];
     BvhView view;
-    const uint32_t sph_root = stage_tree<kLds>(p, lds, view);  // the sphere walk's first node
+    const uint32_t sph_root = stage_tree<kLds, kCorner>(p, corner, lds, view);  // the sphere walk's first node
     // kMesh 3: the lane's stack of wide-node indices (u16, entry k at
     // tstack[k * blockDim.x]) after the sphere tree's LDS copy
     uint16_t *const tstack = reinterpret_cast<uint16_t *>(
@@ -1164,7 +1250,8 @@ void trace_kernel(TraceParams p) {
                     best_i = -1;
                     if (kBvh) {
                         spheres_big(p, org, dir, best_t, best_i);
-                        node = sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
+                        node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
+                                                         : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
                         // (RT_AMD_ABLATE=1: timing-only diagnostic, results are wrong)
                         phase = (p.ablate & 1u) ? kTriInit : kSph;
                         if (!kMesh && bounce == 0 && (spl1 >> 16) != kSphListWalk) {
@@ -1206,40 +1293,53 @@ void trace_kernel(TraceParams p) {
                 walked = true;
                 constexpr uint32_t kEnd = kLds ? 0xFFFFu : kNodeEndDev;
                 const SphBound bnd = sph_bound(p, org);
-                F3 nlo, nhi;
-                sphere_slabs(org, inv, sph_inflation(p, bnd, best_t), nlo, nhi);
-                const uint32_t ooff = kLds ? 4u * oct : oct;
+                if (kCorner) {
+                    // corner records: the same nodes in the same order with the
+                    // same skip decisions (sphere_node_corner), fewer VALU per node
+                    F3 nn, nf;
+                    sphere_corner_slabs(org, inv, sph_inflation(p, bnd, best_t), oct, nn, nf);
+                    const uint32_t offn = sph_root + 16u * oct, offf = sph_root + 112u - 16u * oct;
+                    do {
+                        uint32_t leaf;
+                        if (sphere_node_corner(offn, offf, inv, best_t, nn, nf, node, leaf, node_tests))
+                            sphere_leaf(view, org, dir, leaf, best_t, best_i, sph_tests);
+                    } while (node != 0xFFFFu && (!kStep || --budget != 0));
+                } else {
+                    F3 nlo, nhi;
+                    sphere_slabs(org, inv, sph_inflation(p, bnd, best_t), nlo, nhi);
+                    const uint32_t ooff = kLds ? 4u * oct : oct;
 #ifdef RT_WALK_MIX
-                uint32_t wi = 0, wl = 0, wt = 0;
+                    uint32_t wi = 0, wl = 0, wt = 0;
 #endif
-                do {
-                    uint32_t leaf;
-                    const bool lf = sphere_node<kLds>(view, inv, ooff, best_t, nlo, nhi, node, leaf, node_tests);
+                    do {
+                        uint32_t leaf;
+                        const bool lf = sphere_node<kLds>(view, inv, ooff, best_t, nlo, nhi, node, leaf, node_tests);
+#ifdef RT_WALK_MIX
+                        if (kCount) {
+                            ++wi;
+                            const bool any1 = __ballot(lf) != 0;
+                            const bool any2 = __ballot(lf && (leaf & 7u) >= 2u) != 0;
+                            wl += any1 ? 1u : 0u;
+                            wt += any2 ? 2u : any1 ? 1u : 0u;
+                        }
+#endif
+                        if (lf) sphere_leaf(view, org, dir, leaf, best_t, best_i, sph_tests);
+                    } while (node != kEnd && (!kStep || --budget != 0));
 #ifdef RT_WALK_MIX
                     if (kCount) {
-                        ++wi;
-                        const bool any1 = __ballot(lf) != 0;
-                        const bool any2 = __ballot(lf && (leaf & 7u) >= 2u) != 0;
-                        wl += any1 ? 1u : 0u;
-                        wt += any2 ? 2u : any1 ? 1u : 0u;
+                        // (wave maxima over the walking lanes: the longest-active lane saw every iteration)
+                        for (uint32_t off = 1; off < kWave; off <<= 1) {
+                            wi = max(wi, (uint32_t)__shfl_xor((int)wi, (int)off));
+                            wl = max(wl, (uint32_t)__shfl_xor((int)wl, (int)off));
+                            wt = max(wt, (uint32_t)__shfl_xor((int)wt, (int)off));
+                        }
+                        wm_iters += wi;
+                        wm_leaf_iters += wl;
+                        wm_leaf_trips += wt;
+                        wm_walks += 1u;
                     }
 #endif
-                    if (lf) sphere_leaf(view, org, dir, leaf, best_t, best_i, sph_tests);
-                } while (node != kEnd && (!kStep || --budget != 0));
-#ifdef RT_WALK_MIX
-                if (kCount) {
-                    // (wave maxima over the walking lanes: the longest-active lane saw every iteration)
-                    for (uint32_t off = 1; off < kWave; off <<= 1) {
-                        wi = max(wi, (uint32_t)__shfl_xor((int)wi, (int)off));
-                        wl = max(wl, (uint32_t)__shfl_xor((int)wl, (int)off));
-                        wt = max(wt, (uint32_t)__shfl_xor((int)wt, (int)off));
-                    }
-                    wm_iters += wi;
-                    wm_leaf_iters += wl;
-                    wm_leaf_trips += wt;
-                    wm_walks += 1u;
                 }
-#endif
                 if (node == kEnd) phase = kTriInit;
             }
             if (phase == kTriInit) {
@@ -1758,6 +1858,34 @@ void trace_kernel(TraceParams p) {
     }
 }
 
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial = false>
+__global__ __launch_bounds__(trace_threads(kLds, kMesh, kSerial ? 2 : kCount ? 1 : 0))
+__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, kSerial ? 2 : kCount ? 1 : 0), 8)))
+void trace_kernel(TraceParams p) {
+    trace_body<kBvh, kLds, kStep, kMesh, kCount, kSerial, false>(p, nullptr);
+}
+
+// The sphere-only frame kernels over the corner records: instances of their
+// own, so that the box-record kernels above stay the code they were (one
+// kernel with both walks behind a launch flag ran its box walk 1.5 % slower:
+// the compiler placed it out of line).  The argument block begins with the
+// TraceParams (trace_body's kargs() re-reads them from offset 0).  They keep
+// trace_kernel's name and parameter list, so tools that parse
+// `trace_kernel<...>` names (tools/pmc_summary.py) tell lean from counting.
+struct CornerParams {
+    TraceParams p;
+    const uint4 *image;  // bvh.h SphereBVH::corner: 8 uint4 per node
+};
+namespace corner {
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial = false>
+__global__ __launch_bounds__(trace_threads(true, 0, kCount ? 1 : 0))
+__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(true, 0, kCount ? 1 : 0), 8)))
+void trace_kernel(CornerParams c) {
+    static_assert(kBvh && kLds && kMesh == 0 && !kSerial, "corner records: sphere-only LDS frame kernels");
+    trace_body<true, true, kStep, 0, kCount, false, true>(c.p, c.image);
+}
+}  // namespace corner
+
 // ------------------------------------------------------------ resolve kernel
 // Sums each pixel's samples in order (common.rs:333-341), gamma + `as u8`
 // (:344-356), one RGBA8 word per pixel.  The slab is planar and pixel-major,
@@ -1827,20 +1955,29 @@ __global__ __launch_bounds__(kResolveWaves * 64) void resolve_kernel(
 
 uint32_t trace_block_threads(bool lds, int mesh, int kind) { return trace_threads(lds, mesh, kind); }
 
-size_t trace_lds_bytes(const TraceParams &p) {
+size_t trace_lds_bytes(const TraceParams &p, bool corner) {
     // (shading records in global memory instead, which would allow 8 waves per
     // SIMD: A/B +1.7 % at 6 waves, +8 % at 8 waves per SIMD)
-    return trace_tree_lds(p.nnodes, p.nprims, p.nsph_padded);
+    // (the corner records do exactly that: twice the node bytes, still two
+    // workgroups of 8 waves per SIMD per CU)
+    return corner ? trace_corner_lds(p.nnodes, p.nprims) : trace_tree_lds(p.nnodes, p.nprims, p.nsph_padded);
 }
 
-size_t trace_dyn_lds(const TraceParams &p, bool lds, bool wide, uint32_t threads) {
-    const size_t tree = lds ? (trace_lds_bytes(p) + 15u) & ~(size_t)15u : 0u;
+size_t trace_dyn_lds(const TraceParams &p, bool lds, bool wide, uint32_t threads, bool corner) {
+    const size_t tree = lds ? (trace_lds_bytes(p, corner) + 15u) & ~(size_t)15u : 0u;
     return tree + (wide ? (size_t)p.tw_depth * threads * 2u : 0u);
 }
 
 template <bool kStep, int kMesh, bool kCount, bool kSerial>
-static void launch_trace_t(const TraceParams &p, uint32_t blocks, hipStream_t stream) {
+static void launch_trace_t(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner) {
     const uint32_t lt = trace_threads(true, kMesh, kSerial ? 2 : kCount ? 1 : 0);
+    if constexpr (kMesh == 0 && !kSerial) {
+        if (p.nnodes && p.use_lds && corner != nullptr) {
+            hipLaunchKernelGGL((corner::trace_kernel<true, true, kStep, 0, kCount, false>), dim3(blocks), dim3(lt),
+                               trace_dyn_lds(p, true, false, lt, true), stream, CornerParams{p, corner});
+            return;
+        }
+    }
     if (p.nnodes && p.use_lds)
         hipLaunchKernelGGL((trace_kernel<true, true, kStep, kMesh, kCount, kSerial>), dim3(blocks), dim3(lt),
                            trace_dyn_lds(p, true, kMesh == 3, lt), stream, p);
@@ -1855,30 +1992,30 @@ static void launch_trace_t(const TraceParams &p, uint32_t blocks, hipStream_t st
 // kMesh: 0 no triangles, 1 brute-force triangles (no triangle tree: small
 // meshes), 2 triangle trees -- the tree walk's registers only where it runs
 template <bool kCount, bool kSerial>
-static void launch_trace_c(const TraceParams &p, uint32_t blocks, hipStream_t stream) {
+static void launch_trace_c(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner) {
     const int mesh = trace_mesh_kind(p.ntri != 0, p.tnodes != 0);
     if (!kSerial && mesh == 2 && p.tw_nodes != nullptr) {
-        if (p.step) launch_trace_t<true, 3, kCount, false>(p, blocks, stream);
-        else launch_trace_t<false, 3, kCount, false>(p, blocks, stream);
+        if (p.step) launch_trace_t<true, 3, kCount, false>(p, blocks, stream, nullptr);
+        else launch_trace_t<false, 3, kCount, false>(p, blocks, stream, nullptr);
         return;
     }
     if (p.step) {
-        if (mesh == 2) launch_trace_t<true, 2, kCount, kSerial>(p, blocks, stream);
-        else if (mesh == 1) launch_trace_t<true, 1, kCount, kSerial>(p, blocks, stream);
-        else launch_trace_t<true, 0, kCount, kSerial>(p, blocks, stream);
+        if (mesh == 2) launch_trace_t<true, 2, kCount, kSerial>(p, blocks, stream, corner);
+        else if (mesh == 1) launch_trace_t<true, 1, kCount, kSerial>(p, blocks, stream, corner);
+        else launch_trace_t<true, 0, kCount, kSerial>(p, blocks, stream, corner);
     } else {
-        if (mesh == 2) launch_trace_t<false, 2, kCount, kSerial>(p, blocks, stream);
-        else if (mesh == 1) launch_trace_t<false, 1, kCount, kSerial>(p, blocks, stream);
-        else launch_trace_t<false, 0, kCount, kSerial>(p, blocks, stream);
+        if (mesh == 2) launch_trace_t<false, 2, kCount, kSerial>(p, blocks, stream, corner);
+        else if (mesh == 1) launch_trace_t<false, 1, kCount, kSerial>(p, blocks, stream, corner);
+        else launch_trace_t<false, 0, kCount, kSerial>(p, blocks, stream, corner);
     }
 }
 
 // Frames rendered without stats run a variant whose work counters compile away
 // (one VALU increment per node / sphere test / ray); SERIAL passes their own.
-hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream) {
-    if (p.mode >= kRngSerialCount) launch_trace_c<false, true>(p, blocks, stream);
-    else if (p.stats) launch_trace_c<true, false>(p, blocks, stream);
-    else launch_trace_c<false, false>(p, blocks, stream);
+hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner) {
+    if (p.mode >= kRngSerialCount) launch_trace_c<false, true>(p, blocks, stream, nullptr);
+    else if (p.stats) launch_trace_c<true, false>(p, blocks, stream, corner);
+    else launch_trace_c<false, false>(p, blocks, stream, corner);
     return hipGetLastError();
 }
 
@@ -1895,6 +2032,13 @@ hipError_t launch_resolve_ex(const float *samples, uint32_t *out, uint32_t npix,
 template <bool kStep, int kMesh, bool kCount, bool kSerial>
 static hipError_t trace_occupancy_t(int *blocks_per_cu, int variant, size_t lds_bytes) {
     constexpr int kind = kSerial ? 2 : kCount ? 1 : 0;
+    if constexpr (kMesh == 0 && !kSerial) {
+        if (variant == 3)
+            return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                blocks_per_cu, corner::trace_kernel<true, true, kStep, 0, kCount, false>,
+                trace_threads(true, 0, kind), lds_bytes);
+    }
+    if (variant == 3) return hipErrorInvalidValue;
     if (variant == 2)
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(
             blocks_per_cu, trace_kernel<true, true, kStep, kMesh, kCount, kSerial>,
@@ -1920,6 +2064,41 @@ static hipError_t trace_occupancy_c(int *blocks_per_cu, int variant, size_t lds_
     return mesh == 2   ? trace_occupancy_t<false, 2, kCount, kSerial>(blocks_per_cu, variant, lds_bytes)
            : mesh == 1 ? trace_occupancy_t<false, 1, kCount, kSerial>(blocks_per_cu, variant, lds_bytes)
                        : trace_occupancy_t<false, 0, kCount, kSerial>(blocks_per_cu, variant, lds_bytes);
+}
+
+template <bool kStep, int kMesh, bool kCount, bool kSerial>
+static hipError_t trace_lds_opt_in_t() {
+    hipError_t e = hipFuncSetAttribute(
+        reinterpret_cast<const void *>(&trace_kernel<true, true, kStep, kMesh, kCount, kSerial>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+    if constexpr (kMesh == 0 && !kSerial) {
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(
+                reinterpret_cast<const void *>(&corner::trace_kernel<true, true, kStep, 0, kCount, false>),
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+    }
+    return e;
+}
+template <bool kCount, bool kSerial>
+static hipError_t trace_lds_opt_in_c() {
+    hipError_t e = hipSuccess;
+    auto both = [&](auto mesh) {
+        constexpr int m = decltype(mesh)::value;
+        if (e == hipSuccess) e = trace_lds_opt_in_t<false, m, kCount, kSerial>();
+        if (e == hipSuccess) e = trace_lds_opt_in_t<true, m, kCount, kSerial>();
+    };
+    both(std::integral_constant<int, 0>{});
+    both(std::integral_constant<int, 1>{});
+    both(std::integral_constant<int, 2>{});
+    if constexpr (!kSerial) both(std::integral_constant<int, 3>{});  // (launch_trace_c: frames only)
+    return e;
+}
+
+hipError_t trace_lds_opt_in() {
+    hipError_t e = trace_lds_opt_in_c<false, false>();
+    if (e == hipSuccess) e = trace_lds_opt_in_c<true, false>();
+    if (e == hipSuccess) e = trace_lds_opt_in_c<false, true>();
+    return e;
 }
 
 hipError_t trace_occupancy(int *blocks_per_cu, int variant, size_t lds_bytes, bool step, int mesh,
@@ -2680,7 +2859,7 @@ void serial_coalesce_kernel(TraceParams p, uint32_t *__restrict__ path,
     if (blk >= nb) return;  // (whole workgroup, before any barrier)
     extern __shared__ float4 lds[];
     BvhView view;
-    const uint32_t sph_root = stage_tree<kLds>(p, lds, view);
+    const uint32_t sph_root = stage_tree<kLds, false>(p, nullptr, lds, view);
     const uint32_t depth = p.depth > 0 ? (uint32_t)p.depth : 0u;
     const uint32_t Kp = K + depth + 1, W = (Kp + 31) / 32;
     auto al = [](uint32_t x) { return (x + 15u) & ~15u; };

@@ -50,7 +50,7 @@ DeviceState::~DeviceState() {
     if (device < 0) return;
     if (hipSetDevice(device) != hipSuccess) return;
     void *bufs[] = {sph_hot, sph_cold, tri_hot, tri_geo, mats, samples, ring, out, replay, counter, stats,
-                    bvh_nodes, bvh_prims, big_hot, bvh_miss, bvh_prim_id, big_id, bvh_miss16,
+                    bvh_nodes, bvh_prims, big_hot, bvh_miss, bvh_prim_id, big_id, bvh_miss16, bvh_corner,
                     sph_shade, sph_kind, tbvh_nodes, tbvh_tris, tbvh_loose, tw_nodes, tw_tris,
                     cam_nodes, cam_tris, ptl_off, ptl_items, spl, tile, gath,
                     sstates, stab, sscan, swin, sjump, sctrl, sbend, spath, sfin,
@@ -136,6 +136,15 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
                 }
             return hipSuccess;
         };
+        // LDS trees above 64 KB per workgroup need the kernels' opt-in, before
+        // any occupancy query or launch; a runtime that refuses it keeps the
+        // 64 KB cap (RtRenderStats::sphere_tree reports what a frame walked)
+        size_t lds_cap = kLdsPerCu;
+        if (trace_lds_opt_in() != hipSuccess) {
+            (void)hipGetLastError();
+            lds_cap = kLdsDefaultMax;
+        }
+        lds_cap = std::min<size_t>(lds_cap, env_u64("RT_AMD_LDS_MAX", kLdsPerCu));
         HIP_TRY(occupancy_global());
         // scene upload (once per device)
         const PackedScene &p = w.packed;
@@ -179,8 +188,50 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
             TraceParams lp{};
             lp.nnodes = d->nnodes; lp.nprims = d->nprims; lp.nsph_padded = (uint32_t)p.nsph_padded;
             const size_t lds = trace_lds_bytes(lp);
+            // A tree above the 64 KB every kernel may take by default is staged
+            // only while it costs no workgroup: 160 KiB per CU are shared by the
+            // resident workgroups, so the instance must keep the workgroups per
+            // CU it has at 64 KB (the lean sphere kernel: 2 x 1024 threads, i.e.
+            // 80 KB each; losing one costs far more than the LDS walk saves).
+            // bytes: the workgroup's whole request; with the wide triangle
+            // walk's stacks in it (stacks) the 64 KB rule stays as it was.
+            // variant: trace_occupancy's (2 box records, 3 corner records)
+            auto keeps_workgroups = [&](int blocks, size_t bytes, bool stacks, int variant, int st, int mesh,
+                                        int c, bool &ok) -> hipError_t {
+                ok = blocks > 0;
+                if (!ok || bytes <= kLdsDefaultMax) return hipSuccess;
+                ok = false;
+                if (stacks) return hipSuccess;
+                int ref = 0;
+                const hipError_t e = trace_occupancy(&ref, variant, kLdsDefaultMax, st, mesh, c);
+                ok = e == hipSuccess && blocks == ref;
+                return e;
+            };
+            // Corner records (bvh.h SphereBVH::corner) for the sphere-only frame
+            // kernels, lean and counting: 128 B per node, the shading records
+            // left in global memory
+            const size_t corner = trace_corner_lds(d->nnodes, d->nprims);
+            if (!bv.corner.empty() && tri == 0 && corner <= lds_cap) {
+                bool fits = true;
+                for (int c = 0; c < 2 && fits; ++c)
+                    for (int st = 0; st < 2 && fits; ++st) {
+                        // (a query the runtime refuses: the layout does not fit)
+                        if (trace_occupancy(&d->blocks_per_cu_corner[c][st], 3, corner, st, 0, c) != hipSuccess ||
+                            keeps_workgroups(d->blocks_per_cu_corner[c][st], corner, false, 3, st, 0, c, fits) !=
+                                hipSuccess) {
+                            (void)hipGetLastError();
+                            fits = false;
+                        }
+                    }
+                if (fits) {
+                    HIP_TRY(hipMalloc((void **)&d->bvh_corner, bv.corner.size() * 4));
+                    HIP_TRY(hipMemcpy(d->bvh_corner, bv.corner.data(), bv.corner.size() * 4,
+                                      hipMemcpyHostToDevice));
+                    d->corner_bytes = corner;
+                }
+            }
             // (the LDS copy addresses 64-B node records with u16 byte offsets)
-            if (d->nnodes <= kLdsTreeMaxNodes && lds <= env_u64("RT_AMD_LDS_MAX", 64 * 1024)) {
+            if (d->nnodes <= kLdsTreeMaxNodes && lds <= lds_cap) {
                 std::vector<uint16_t> m16(bv.miss.size());
                 for (size_t i = 0; i < m16.size(); ++i)
                     m16[i] = bv.miss[i] == kNodeEnd ? (uint16_t)0xFFFF : (uint16_t)bv.miss[i];
@@ -196,11 +247,14 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
                         for (int st = 0; st < 2; ++st) {
                             const uint32_t lt = trace_block_threads(true, tri == 3 && c == 2 ? 2 : tri, c);
                             const size_t sb = stack_lds(c, lt);
-                            const hipError_t e = trace_occupancy(&d->blocks_per_cu_lds[c][st], 2,
-                                                                 sb ? ((lds + 15u) & ~(size_t)15u) + sb : lds, st,
-                                                                 tri, c);
+                            const size_t total = sb ? ((lds + 15u) & ~(size_t)15u) + sb : lds;
+                            const hipError_t e = trace_occupancy(&d->blocks_per_cu_lds[c][st], 2, total, st, tri, c);
                             if (e != hipSuccess) return e;
-                            fits = fits && d->blocks_per_cu_lds[c][st] > 0;
+                            bool ok = false;
+                            if (keeps_workgroups(d->blocks_per_cu_lds[c][st], total, sb != 0, 2, st, tri, c, ok) !=
+                                hipSuccess)
+                                (void)hipGetLastError();
+                            fits = fits && ok;
                         }
                     return hipSuccess;
                 };
@@ -491,6 +545,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // 251, 256 -> 263, 512 -> 353; 6 waves: 64 -> 243, 96 -> 240, 128 -> 242)
     p.steps = (uint32_t)std::max<uint64_t>(1, env_u64("RT_AMD_STEPS", 128));
     p.row_block = B; p.rank = o.rank; p.nranks = nranks;
+    const uint4 *corner_img = nullptr;  // the LDS tree as corner records (sphere-only frames), else box records
     const bool use_bvh = d->nnodes > 0 && o.accel != RT_ACCEL_BRUTE;
     if (use_bvh) {
         const SphereBVH &bv = w.bvh;
@@ -499,7 +554,14 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         p.big_hot = d->big_hot; p.big_id = d->big_id;
         p.nnodes = d->nnodes; p.nbig = d->nbig; p.nprims = d->nprims;
         p.bvh_miss16 = d->bvh_miss16;
-        p.use_lds = d->lds_bytes > 0 && env_u64("RT_AMD_LDS", 1) != 0;
+        // The LDS layout: corner records for the sphere-only frame kernels when
+        // they fit (RT_AMD_CORNER=0: box records, for A/B runs and tests), box
+        // records for the SERIAL passes and everything else; RT_AMD_LDS=0 or
+        // neither fitting: the walk from global memory
+        const bool lds_on = env_u64("RT_AMD_LDS", 1) != 0;
+        if (lds_on && sp == nullptr && d->corner_bytes > 0 && env_u64("RT_AMD_CORNER", 1) != 0)
+            corner_img = d->bvh_corner;
+        p.use_lds = lds_on && (d->lds_bytes > 0 || corner_img != nullptr);
         for (int k = 0; k < 3; ++k) p.bvh_c[k] = bv.centre[k];
         p.bvh_r = bv.radius; p.bvh_rmax = bv.rmax; p.bvh_mag = bv.mag;
         p.bvh_inv_rmin = env_u64("RT_AMD_LINEAR_E", 0) ? INFINITY : bv.inv_rmin;
@@ -647,6 +709,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // launch_trace runs the counting variant iff p.stats, the SERIAL instances for sp
     const int ctv = sp ? 2 : timed ? 1 : 0;
     const int bpc = !use_bvh   ? d->blocks_per_cu[ctv][sv]
+                    : corner_img ? d->blocks_per_cu_corner[ctv][sv]
                     : p.use_lds ? d->blocks_per_cu_lds[ctv][sv]
                                 : d->blocks_per_cu_bvh[ctv][sv];
     // (the kernel family launch_trace picks: the wide triangle walk for frames)
@@ -737,8 +800,10 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // workgroups, waves, jobs per queue pull (chunk) and job-queue partitions
     struct LaunchPlan { uint64_t blocks, nwaves, chunk, parts, block_threads; };
     auto plan = [&](int k, uint64_t njobs) -> LaunchPlan {
-        const int kb = !use_bvh ? d->blocks_per_cu[k][sv] : p.use_lds ? d->blocks_per_cu_lds[k][sv]
-                                                                     : d->blocks_per_cu_bvh[k][sv];
+        const int kb = !use_bvh    ? d->blocks_per_cu[k][sv]
+                       : corner_img ? d->blocks_per_cu_corner[k][sv]
+                       : p.use_lds ? d->blocks_per_cu_lds[k][sv]
+                                   : d->blocks_per_cu_bvh[k][sv];
         const uint64_t wpb = trace_block_threads(use_bvh && p.use_lds, fam, k) / 64;
         const uint64_t jobs_per_block = wpb * 256;
         uint64_t blocks = std::min<uint64_t>((uint64_t)kb * d->num_cus, (njobs + jobs_per_block - 1) / jobs_per_block);
@@ -824,7 +889,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
             if (!d->cset_clean[d->cset]) HIP_TRY(hipMemsetAsync(cur, 0, parts * 128, s));
             p.job_counter = cur;
             p.job_counter_next = d->counter + (size_t)(d->cset ^ 1u) * kMaxParts * 32;
-            HIP_TRY(launch_trace(p, (uint32_t)blocks, s));
+            HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img));
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
             d->cset_clean[d->cset] = true;
@@ -884,6 +949,8 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     fx.launch_wsteps = p.wsteps;
     fx.launch_block_threads = (uint32_t)lean_plan.block_threads;
     fx.launch_blocks = (uint32_t)lean_plan.blocks;
+    fx.sphere_tree = !use_bvh ? 0u : !p.use_lds ? 1u : corner_img ? 3u : 2u;
+    fx.sphere_tree_lds_bytes = use_bvh && p.use_lds ? (uint32_t)trace_lds_bytes(p, corner_img != nullptr) : 0u;
     fx.nsph = d->nsph;
     fx.ntri = d->ntri;
     fx.nbig = d->nbig;
@@ -937,6 +1004,8 @@ int collect_frame_stats(DeviceState *d, RtRenderStats *stats) {
         stats->launch_wsteps = fx.launch_wsteps;
         stats->launch_block_threads = fx.launch_block_threads;
         stats->launch_blocks = fx.launch_blocks;
+        stats->sphere_tree = fx.sphere_tree;
+        stats->sphere_tree_lds_bytes = fx.sphere_tree_lds_bytes;
         stats->accel = fx.accel;
         stats->bvh_sphere_tests = st[2];
         stats->bvh_node_tests = st[3];
@@ -1744,6 +1813,7 @@ int render_frame_multi(WorldState &w, const CameraModel &cam, size_t width, size
             stats->launch_refill_min = sg.launch_refill_min; stats->launch_walk_min = sg.launch_walk_min;
             stats->launch_tri_walk_min = sg.launch_tri_walk_min; stats->launch_wsteps = sg.launch_wsteps;
             stats->launch_block_threads = sg.launch_block_threads; stats->launch_blocks = sg.launch_blocks;
+            stats->sphere_tree = sg.sphere_tree; stats->sphere_tree_lds_bytes = sg.sphere_tree_lds_bytes;
         }
     }
     HIP_TRY(hipSetDevice(devs[0]));

@@ -27,6 +27,7 @@ struct RtRenderStatsFixed {
     uint32_t launch_parts = 0, launch_chunk = 0, launch_refill_min = 0, launch_walk_min = 0;
     uint32_t launch_tri_walk_min = 0, launch_wsteps = 0, launch_block_threads = 0, launch_blocks = 0;
     uint32_t nsph = 0, ntri = 0, nbig = 0;
+    uint32_t sphere_tree = 0, sphere_tree_lds_bytes = 0;
 };
 
 void set_error(const std::string &msg);
@@ -72,6 +73,11 @@ struct DeviceState {
     size_t gspl_w = 0, gspl_h = 0;
     bool gspl_built = false, gspl_ok = false;
     size_t lds_bytes = 0;                                      // 0: tree not LDS-stageable
+    // corner records (bvh.h SphereBVH::corner), uploaded when the sphere-only
+    // frame kernels can stage them without losing a workgroup per CU
+    uint4 *bvh_corner = nullptr;
+    size_t corner_bytes = 0;                                   // 0: box records (or no LDS tree)
+    int blocks_per_cu_corner[2][2] = {};                       // [lean, counting][step]
     float *samples = nullptr;        size_t samples_cap = 0;   // sample slab (3 planes)
     float *ring = nullptr;           size_t ring_cap = 0;      // per-wave sample rings (fused resolve)
     uint32_t *out = nullptr;         size_t out_cap = 0;       // RGBA8 tile (host path)

@@ -75,7 +75,8 @@ class RenderStats(C.Structure):
                 ("launch_parts", C.c_uint32), ("launch_chunk", C.c_uint32),
                 ("launch_refill_min", C.c_uint32), ("launch_walk_min", C.c_uint32),
                 ("launch_tri_walk_min", C.c_uint32), ("launch_wsteps", C.c_uint32),
-                ("launch_block_threads", C.c_uint32), ("launch_blocks", C.c_uint32)]
+                ("launch_block_threads", C.c_uint32), ("launch_blocks", C.c_uint32),
+                ("sphere_tree", C.c_uint32), ("sphere_tree_lds_bytes", C.c_uint32)]
 
     def as_dict(self):
         out = {}
