@@ -364,7 +364,9 @@ __host__ __device__ inline size_t trace_tree_lds(uint32_t nnodes, uint32_t nprim
 // the corner-record copy: 128-B node records, prims and ids (shading records
 // and kinds stay in global memory)
 __host__ __device__ inline size_t trace_corner_lds(uint32_t nnodes, uint32_t nprims) {
-    return (size_t)nnodes * 128 + (size_t)nprims * 20;
+    // (+ 16: sphere_leaf reads entry first + 1 of a one-sphere leaf unused, for the
+    // last entry the 16 B and the word after the image's end)
+    return (size_t)nnodes * 128 + (size_t)nprims * 20 + 16;
 }
 // LDS of one CU, shared by its resident workgroups; a kernel takes more than
 // kLdsDefaultMax per workgroup only after trace_lds_opt_in

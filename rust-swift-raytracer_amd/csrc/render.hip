@@ -464,6 +464,11 @@ __device__ __forceinline__ void sphere_slabs(F3 org, F3 inv, float e, F3 &nlo, F
 // best t at the walk's start: a larger best t only inflates them more (still
 // exact), and re-deriving it after every new best (the round-1
 // to round-4 code) cost ~20 VALU per improvement for boxes ~1 % tighter.
+// kAhead (LDS copies only): the second sphere's record and index are read
+// with the first one's, before the first test, so a two-sphere leaf waits for
+// the LDS once; a one-sphere leaf's read of entry first + 1 stays inside the
+// workgroup's LDS image (the id words follow the records) and is not used.
+template <bool kAhead = false>
 __device__ __forceinline__ void sphere_leaf(const BvhView &v, F3 org, F3 dir, uint32_t leaf, float &best_t,
                                             int &best_i, uint32_t &sph_tests) {
     const uint32_t first = leaf >> 3, n = leaf & 7u;
@@ -471,9 +476,19 @@ __device__ __forceinline__ void sphere_leaf(const BvhView &v, F3 org, F3 dir, ui
     // leaves hold 1 or 2 spheres (leaf size 2): straight-line tests, the loop
     // only for larger leaves (RT_AMD_LEAF)
     sph_tests += n;
+    float4 S1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int i1 = 0;
+    if (kAhead) {
+        S1 = v.prims[first + 1];
+        i1 = (int)v.ids[first + 1];
+    }
     sphere_candidate(v.prims[first], org, dir, (int)v.ids[first], best_t, best_i);
     if (n > 1u) {
-        sphere_candidate(v.prims[first + 1], org, dir, (int)v.ids[first + 1], best_t, best_i);
+        if (!kAhead) {
+            S1 = v.prims[first + 1];
+            i1 = (int)v.ids[first + 1];
+        }
+        sphere_candidate(S1, org, dir, i1, best_t, best_i);
         for (uint32_t j = first + 2; j < first + n; ++j)
             sphere_candidate(v.prims[j], org, dir, (int)v.ids[j], best_t, best_i);
     }
@@ -822,14 +837,18 @@ __device__ __forceinline__ void tri_primary_list(const TraceParams &p, uint32_t 
 
 // One resolved pixel: gamma + `as u8` (common.rs:344-356), RGBA8 at the
 // tile row of launch-local pixel lp.
-__device__ __forceinline__ void resolve_store(const TraceParams &p, uint32_t lp, float r, float g,
-                                              float b) {
-    const uint32_t R = sat_u8(__builtin_sqrtf(r * p.inv_spp) * 255.999f);
-    const uint32_t G = sat_u8(__builtin_sqrtf(g * p.inv_spp) * 255.999f);
-    const uint32_t B = sat_u8(__builtin_sqrtf(b * p.inv_spp) * 255.999f);
+__device__ __forceinline__ uint32_t resolve_channel(const TraceParams &p, float sum) {
+    return sat_u8(__builtin_sqrtf(sum * p.inv_spp) * 255.999f);
+}
+__device__ __forceinline__ void resolve_store_u8(const TraceParams &p, uint32_t lp, uint32_t R, uint32_t G,
+                                                 uint32_t B) {
     const uint32_t q = fdiv(lp, p.div_width);
     const uint32_t col = lp - q * p.width;
     p.out[(size_t)(p.slab_row0 + q) * p.width + col] = R | (G << 8) | (B << 16) | (p.alpha_u8 << 24);
+}
+__device__ __forceinline__ void resolve_store(const TraceParams &p, uint32_t lp, float r, float g,
+                                              float b) {
+    resolve_store_u8(p, lp, resolve_channel(p, r), resolve_channel(p, g), resolve_channel(p, b));
 }
 
 // Fused resolve of one finished chunk (wave-uniform call, all lanes active):
@@ -841,7 +860,8 @@ __device__ __forceinline__ void resolve_store(const TraceParams &p, uint32_t lp,
 //
 // One lane per (pixel, plane) when 3 * pixels <= 64 and spp % 4 == 0: lane
 // c * np + g folds plane c of pixel g in sample order from float4 loads (4
-// in flight per round), then the pixel's lane collects the G and B sums with
+// in flight per round) and converts its own sum (gamma + `as u8`, one pass
+// for the three planes), then the pixel's lane collects the G and B bytes with
 // two shuffles: spp adds and spp / 4 loads per lane (A/B on C2 -1.7 %
 // against folding float4 groups through ds_bpermute, 3 * spp bpermutes and
 // adds per pixel).  Other chunks, and the triangle kernels (kPlaneLanes
@@ -882,9 +902,13 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
                 }
             }
         }
-        const float sg = __shfl(acc, (int)(lane < np ? np + lane : lane));
-        const float sb = __shfl(acc, (int)(lane < np ? 2u * np + lane : lane));
-        if (lane < np) resolve_store(p, pix0 + lane, acc, sg, sb);
+        // gamma + `as u8` of the lane's own plane sum (resolve_store's
+        // operations on the same value: the same byte), one pass for the
+        // three planes; the pixel's lane then collects the G and B bytes
+        const uint32_t ch = resolve_channel(p, acc);
+        const uint32_t G = (uint32_t)__shfl((int)ch, (int)(lane < np ? np + lane : lane));
+        const uint32_t B = (uint32_t)__shfl((int)ch, (int)(lane < np ? 2u * np + lane : lane));
+        if (lane < np) resolve_store_u8(p, pix0 + lane, ch, G, B);
         return;
     }
     for (uint32_t i = lane; i < np; i += kWave) {
@@ -1131,6 +1155,11 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
     // lane state between loop iterations (see the bounce loop below)
     enum : uint32_t { kSetup = 0, kSph = 1, kTriInit = 2, kTri = 3, kShade = 4 };
     uint32_t phase = kSetup, node = 0, oct = 0;
+    // Sphere-only kernels whose walk is not sliced read inv, oct and node only
+    // inside the sphere walk, which starts and ends in one iteration: they are
+    // derived there (not loop-carried, and not at all for rays that do not
+    // walk).  Sliced walks resume at `node`, the triangle walks read inv.
+    constexpr bool kWalkState = kMesh == 0 && !kStep;
     float best_t = 0.0f, tri_t = 0.0f, e = 0.0f;  // e: the triangle walk's margin rho
     int best_i = -1, tri_i = -1;
     bool active = false;
@@ -1243,15 +1272,19 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     // t values scaled by 1e20|d| < 1, which keeps its interval's sign
                     // pattern -- the ray lies inside that (inflated) slab for any
                     // finite hit, and the scaled interval still spans [0, >1e9].
-                    inv = f3(slab_rcp(dir.x), slab_rcp(dir.y), slab_rcp(dir.z));
-                    oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+                    // (kWalkState: derived at the sphere walk instead, see there)
+                    if (!kWalkState) {
+                        inv = f3(slab_rcp(dir.x), slab_rcp(dir.y), slab_rcp(dir.z));
+                        oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+                    }
                     // World::hit, spheres in order with shrinking t_max (common.rs:241-247)
                     best_t = __builtin_inff();
                     best_i = -1;
                     if (kBvh) {
                         spheres_big(p, org, dir, best_t, best_i);
-                        node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
-                                                         : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
+                        if (!kWalkState)
+                            node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
+                                           : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
                         // (RT_AMD_ABLATE=1: timing-only diagnostic, results are wrong)
                         phase = (p.ablate & 1u) ? kTriInit : kSph;
                         if (!kMesh && bounce == 0 && (spl1 >> 16) != kSphListWalk) {
@@ -1293,6 +1326,17 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                 walked = true;
                 constexpr uint32_t kEnd = kLds ? 0xFFFFu : kNodeEndDev;
                 const SphBound bnd = sph_bound(p, org);
+                if (kWalkState) {
+                    // the walk's own inputs, with its other per-ray values: an
+                    // unsliced walk ends in this iteration, so they are derived
+                    // once per walking ray and never for a ray whose primary
+                    // sphere list replaces the walk (the clamp and the sign
+                    // rule of the ray setup above, the same operations)
+                    inv = f3(slab_rcp(dir.x), slab_rcp(dir.y), slab_rcp(dir.z));
+                    oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+                    node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
+                                   : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
+                }
                 if (kCorner) {
                     // corner records: the same nodes in the same order with the
                     // same skip decisions (sphere_node_corner), fewer VALU per node
@@ -1302,7 +1346,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     do {
                         uint32_t leaf;
                         if (sphere_node_corner(offn, offf, inv, best_t, nn, nf, node, leaf, node_tests))
-                            sphere_leaf(view, org, dir, leaf, best_t, best_i, sph_tests);
+                            sphere_leaf<true>(view, org, dir, leaf, best_t, best_i, sph_tests);
                     } while (node != 0xFFFFu && (!kStep || --budget != 0));
                 } else {
                     F3 nlo, nhi;
@@ -1323,7 +1367,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                             wt += any2 ? 2u : any1 ? 1u : 0u;
                         }
 #endif
-                        if (lf) sphere_leaf(view, org, dir, leaf, best_t, best_i, sph_tests);
+                        if (lf) sphere_leaf<kLds>(view, org, dir, leaf, best_t, best_i, sph_tests);
                     } while (node != kEnd && (!kStep || --budget != 0));
 #ifdef RT_WALK_MIX
                     if (kCount) {

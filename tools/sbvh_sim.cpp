@@ -7,8 +7,28 @@
 // Not product code, not a parity check (double arithmetic, no inflation).
 //   g++ -O2 -std=c++17 -I../rust-swift-raytracer_amd/csrc sbvh_sim.cpp \
 //       ../rust-swift-raytracer_amd/csrc/{bvh,scene}.cpp -o sbvh_sim -lpthread
-//   ./sbvh_sim ../scenes/rtow.txt [W H]     (RT_AMD_LEAF: leaf size, default 3;
+//   ./sbvh_sim ../scenes/rtow.txt [W H [S]] (S samples per pixel, pixel-major like
+//   the kernel's jobs, default 1; RT_AMD_LEAF: leaf size, default 3;
 //   SIM_BVH4=1: node fetches and box tests of the tree collapsed to 4-wide nodes)
+// SIM_WAVE=1: lock-step wave cost of the walk loop.  The walks of one bounce
+// (SIM_WAVE_BOUNCE, default 1) are recorded visit by visit -- started at the
+// root's near child like the LDS walks -- and replayed 64 consecutive walks
+// per wave the way the kernel's loop runs them: one node step per trip for
+// the lanes still walking, and in trips where some lane entered a leaf the
+// leaf code, sphere by sphere: a discriminant for the lanes whose leaf holds
+// that sphere, a root-and-merge pass when one of them is >= 0.  Reports trips,
+// leaf trips, lanes per leaf trip, root passes and a VALU estimate per wave
+// walk from per-step costs read off the compiled kernel (SIM_COST_NODE 16,
+// SIM_COST_LEAF 19 per discriminant, SIM_COST_ROOT 22 per root-and-merge
+// pass, SIM_COST_SELECT 4), for the loop as it is and for two variants:
+//   merged roots: all of a leaf's discriminants first, then one root pass for
+//     each lane's first sphere with a root (+ the selects) and further passes
+//     only while some lane has another;
+//   gated leaf tests (SIM_WAVE_GATE=T, default 1 2 4 8 16 32): lanes that
+//     entered a leaf wait until T lanes have or no lane can step without one;
+//     every loop trip then also pays the gate's own VALU (SIM_COST_GATE 3:
+//     two selects that hold the leaf word and the pending flag, the compare
+//     behind the ballot).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -42,7 +62,11 @@ static double sphere_t(V o, V d, const float *s) {  // (cx, cy, cz, r^2), |d| = 
 
 // the kernel's walk: big spheres, then the tree from the root along the
 // octant links; returns node visits
-static int walk(const SphereBVH &b, const std::vector<float> &hot, V o, V d, Hit &h) {
+// ev (SIM_WAVE): one byte per visit, the entered leaf's sphere count (0: none)
+// | a bit per sphere with a discriminant >= 0 << 3; the walk then starts at
+// the root's near child
+static int walk(const SphereBVH &b, const std::vector<float> &hot, V o, V d, Hit &h,
+                std::vector<uint8_t> *ev = nullptr) {
     for (uint32_t i : b.big) {
         const double t = sphere_t(o, d, &hot[(size_t)i * 4]);
         if (t < h.t) { h.t = t; h.id = (int)i; }
@@ -51,6 +75,12 @@ static int walk(const SphereBVH &b, const std::vector<float> &hot, V o, V d, Hit
     const uint32_t oct = (inv[0] < 0 ? 1u : 0u) | (inv[1] < 0 ? 2u : 0u) | (inv[2] < 0 ? 4u : 0u);
     int visits = 0;
     uint32_t node = 0;
+    if (ev && b.nodes.size() > 8) {
+        uint32_t a, ax;
+        std::memcpy(&a, &b.nodes[3], 4);
+        std::memcpy(&ax, &b.nodes[7], 4);
+        if (!(a & kLeafBit)) node = a + ((oct >> ax) & 1u);
+    }
     while (node != kNodeEnd) {
         ++visits;
         const float *n = &b.nodes[(size_t)node * 8];
@@ -65,11 +95,19 @@ static int walk(const SphereBVH &b, const std::vector<float> &hot, V o, V d, Hit
         std::memcpy(&bb, &n[7], 4);
         const bool skip = tn > tf || tf < 1e-3 || tn > h.t;
         const bool leaf = a & kLeafBit;
-        if (!skip && leaf)
+        uint8_t e = 0;
+        if (!skip && leaf) {
+            e = (uint8_t)std::min(bb, 5u);
             for (uint32_t j = a & ~kLeafBit; j < (a & ~kLeafBit) + bb; ++j) {
-                const double t = sphere_t(o, d, &b.prims[(size_t)j * 4]);
+                const float *sp = &b.prims[(size_t)j * 4];
+                const V oc = sub(o, V{sp[0], sp[1], sp[2]});
+                const double hb = dot(oc, d);
+                if (hb * hb - (dot(oc, oc) - sp[3]) >= 0 && j - (a & ~kLeafBit) < 5) e |= 8u << (j - (a & ~kLeafBit));
+                const double t = sphere_t(o, d, sp);
                 if (t < h.t) { h.t = t; h.id = (int)b.prim_id[j]; }
             }
+        }
+        if (ev) ev->push_back(e);
         node = (skip || leaf) ? b.miss[(size_t)node * 8 + oct] : a + ((oct >> bb) & 1u);
     }
     return visits;
@@ -138,14 +176,70 @@ static int walk4(const SphereBVH &b, const std::vector<float> &hot, V o, V d, Hi
     return fetches;
 }
 
+// SIM_WAVE: replays the recorded walks 64 per wave.  merged: the merged-roots
+// leaf code; gate: lanes that entered a leaf wait for `gate` such lanes.
+struct WaveCost { double trips = 0, leaf_trips = 0, leaf_lanes = 0, roots = 0, valu = 0; size_t waves = 0; };
+static WaveCost wave_cost(const std::vector<std::vector<uint8_t>> &w, bool merged, int gate, const double c[5]) {
+    WaveCost r;
+    for (size_t g = 0; g + 64 <= w.size(); g += 64) {
+        size_t pos[64] = {0};
+        bool pend[64] = {false};
+        ++r.waves;
+        for (;;) {
+            int act = 0, step = 0, npend = 0;
+            for (int l = 0; l < 64; ++l) {
+                if (pos[l] >= w[g + l].size()) continue;
+                ++act;
+                if (pend[l]) continue;
+                ++step;
+                if (w[g + l][pos[l]] & 7) pend[l] = true; else ++pos[l];
+            }
+            if (!act) break;
+            ++r.trips;
+            if (step) r.valu += c[0];
+            if (gate) r.valu += c[4];
+            for (int l = 0; l < 64; ++l) npend += pend[l] ? 1 : 0;
+            // (the loop as it is: gate 0, every entered leaf is tested in its trip)
+            if (!npend || (npend < gate && npend < act)) continue;
+            ++r.leaf_trips;
+            r.leaf_lanes += npend;
+            int maxn = 0, maxroots = 0;
+            bool root_at[5] = {false, false, false, false, false};
+            for (int l = 0; l < 64; ++l) {
+                if (!pend[l]) continue;
+                const uint8_t e = w[g + l][pos[l]];
+                maxn = std::max(maxn, e & 7);
+                int nr = 0;
+                for (int k = 0; k < 5; ++k)
+                    if (e & (8u << k)) { root_at[k] = true; ++nr; }
+                maxroots = std::max(maxroots, nr);
+                pend[l] = false;
+                ++pos[l];
+            }
+            r.valu += c[1] * maxn;
+            int passes = 0;
+            if (merged) {
+                passes = maxroots;
+                if (maxn > 1) r.valu += c[3];
+            } else {
+                for (int k = 0; k < maxn; ++k) passes += root_at[k] ? 1 : 0;
+            }
+            r.roots += passes;
+            r.valu += c[2] * passes;
+        }
+    }
+    return r;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: sbvh_sim scene.txt [W H]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: sbvh_sim scene.txt [W H [S]]\n"); return 2; }
     std::ifstream f(argv[1]);
     std::stringstream ss;
     ss << f.rdbuf();
     SceneModel s;
     if (parse_scene(ss.str(), s) != kParseOk) { std::fprintf(stderr, "parse error\n"); return 1; }
     const int W = argc > 3 ? std::atoi(argv[2]) : 192, H = argc > 3 ? std::atoi(argv[3]) : 108;
+    const int S = argc > 4 ? std::atoi(argv[4]) : 1;
     const char *lf = std::getenv("RT_AMD_LEAF");
     const SphereBVH b = build_sphere_bvh(s.spheres, lf ? (uint32_t)std::atoi(lf) : 3u);
     std::vector<float> hot(s.spheres.size() * 4);
@@ -160,9 +254,13 @@ int main(int argc, char **argv) {
     std::vector<int> vis[3];  // bounce 0, 1, 2
     const bool bvh4 = std::getenv("SIM_BVH4") != nullptr;
     std::vector<int> box4[3];  // SIM_BVH4: children tested per walk
+    const bool wave = std::getenv("SIM_WAVE") != nullptr;
+    const int wave_bounce = std::getenv("SIM_WAVE_BOUNCE") ? std::atoi(std::getenv("SIM_WAVE_BOUNCE")) : 1;
+    std::vector<std::vector<uint8_t>> events;  // SIM_WAVE: the recorded walks
     for (int j = 0; j < H; ++j)
-        for (int i = 0; i < W; ++i) {
-            const double u = (i + rnd()) / (W - 1), v = (j + rnd()) / (H - 1);
+        for (int i = 0; i < W * S; ++i) {
+            const int px = i / S;
+            const double u = (px + rnd()) / (W - 1), v = (j + rnd()) / (H - 1);
             V o = org;
             V d = unit(sub(add(add(V{cm.lower_left.x, cm.lower_left.y, cm.lower_left.z},
                                    mul(V{cm.horizontal.x, cm.horizontal.y, cm.horizontal.z}, u)),
@@ -175,7 +273,9 @@ int main(int argc, char **argv) {
                     vis[bounce].push_back(walk4(b, hot, o, d, h2, &tests));
                     box4[bounce].push_back(tests);
                 }
-                const int v2 = walk(b, hot, o, d, h);
+                const bool rec = wave && bounce == wave_bounce;
+                if (rec) events.emplace_back();
+                const int v2 = walk(b, hot, o, d, h, rec ? &events.back() : nullptr);
                 if (!bvh4) vis[bounce].push_back(v2);
                 if (h.id < 0) break;
                 const float *c = &hot[(size_t)h.id * 4];
@@ -187,6 +287,34 @@ int main(int argc, char **argv) {
             }
         }
     std::printf("nodes %zu leaves<=%s big %zu\n", b.nodes.size() / 8, lf ? lf : "3", b.big.size());
+    if (wave) {
+        auto envd = [](const char *k, double dflt) { const char *v = std::getenv(k); return v ? std::atof(v) : dflt; };
+        const double c[5] = {envd("SIM_COST_NODE", 16), envd("SIM_COST_LEAF", 19), envd("SIM_COST_ROOT", 22),
+                             envd("SIM_COST_SELECT", 4), envd("SIM_COST_GATE", 3)};
+        double visits = 0;
+        for (auto &e : events) visits += e.size();
+        std::printf("wave cost, bounce %d: %zu walks, %.1f visits per walk; costs node %.0f leaf %.0f root %.0f select %.0f gate %.0f\n",
+                    wave_bounce, events.size(), events.empty() ? 0.0 : visits / events.size(), c[0], c[1], c[2], c[3],
+                    c[4]);
+        auto line = [&](const char *name, const WaveCost &r, double base) {
+            const double n = r.waves ? (double)r.waves : 1.0;
+            std::printf("  %-16s trips %.1f, leaf trips %.2f with %.1f lanes, root passes %.2f, VALU %.0f per wave walk"
+                        " (%+.1f%%)\n", name, r.trips / n, r.leaf_trips / n, r.leaf_trips ? r.leaf_lanes / r.leaf_trips : 0.0,
+                        r.roots / n, r.valu / n, base > 0 ? 100.0 * (r.valu / n / base - 1.0) : 0.0);
+        };
+        const WaveCost base = wave_cost(events, false, 0, c);
+        const double bv = base.waves ? base.valu / base.waves : 0.0;
+        line("as it is", base, bv);
+        line("merged roots", wave_cost(events, true, 0, c), bv);
+        const char *gs = std::getenv("SIM_WAVE_GATE");
+        for (int t : {1, 2, 4, 8, 16, 32}) {
+            const int T = gs ? std::max(1, std::atoi(gs)) : t;
+            char name[32];
+            std::snprintf(name, sizeof name, "gated, T = %d", T);
+            line(name, wave_cost(events, false, T, c), bv);
+            if (gs) break;
+        }
+    }
     for (int k = 0; k < 3; ++k) {
         std::vector<int> v = vis[k];
         if (v.empty()) continue;
