@@ -207,7 +207,7 @@ struct PrimarySphereLists {
 };
 PrimarySphereLists build_primary_sphere_lists(const SphereBVH &bv, const CameraModel &cam,
                                               size_t width, size_t height);
-// The same build on the device (render.hip launch_sphere_lists): the host
+// The same build on the device (serial.hip launch_sphere_lists): the host
 // checks and the per-frame constants; false = no lists (every primary ray walks).
 struct SphereListParams {
     double Mi[9];          // inverse camera map, row-major

@@ -44,7 +44,7 @@ constexpr uint32_t kStatSlots = 16;
 constexpr uint32_t kStampSegs = 8;
 
 // SERIAL prediction, per pixel (built on the device from the estimate pass,
-// render.hip launch_serial_tables): P[q] = sum over pixels p < q of spp mu[p]
+// serial.hip launch_serial_tables): P[q] = sum over pixels p < q of spp mu[p]
 // (npix + 1 doubles), mu[p] the pixel's mean scatter count per sample.  The
 // predicted scatter count of frame samples [0, j) is
 // M(j) = P[p] + (j - p spp) mu[p], p = j / spp (P[npix] for j = npix spp).
@@ -204,9 +204,51 @@ RT_HOST_DEVICE inline uint32_t serial_lo(const SerialPred &M, uint32_t a, uint32
     return (uint32_t)c;
 }
 
+// The kernel family of a scene: 0 no triangles, 1 triangles searched by brute
+// force (no triangle tree), 2 triangle trees (TraceParams::tnodes != 0)
+inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : tree ? 2 : 1; }
+
+// One trace_kernel / corner::trace_kernel instance (render.hip trace_instance
+// spells each of them once).
+//   search: the sphere search (RtRenderStats::sphere_tree reports it)
+//   step:   the sliced-walk kernel (TraceParams::step)
+//   mesh:   trace_mesh_kind, or 3: triangle trees walked through the 4-wide
+//           image (TraceParams::tw_nodes)
+//   kind:   what the jobs are
+enum : int { kSearchBrute = 0, kSearchGlobal = 1, kSearchLdsBox = 2, kSearchLdsCorner = 3 };
+enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2 };
+struct TraceVariant {
+    int search;
+    bool step;
+    int mesh;
+    int kind;
+    bool lds() const { return search >= kSearchLdsBox; }
+};
+// The instance that serves a scene of family `mesh` (0-3) searched as `search`:
+// the SERIAL passes keep the binary triangle walk and the box records, and the
+// corner records exist for sphere-only scenes.  The one place these rules live.
+inline TraceVariant trace_variant(int search, bool step, int mesh, int kind) {
+    if (kind == kKindSerial && mesh == 3) mesh = 2;
+    if (search == kSearchLdsCorner && (mesh != 0 || kind == kKindSerial)) search = kSearchLdsBox;
+    return TraceVariant{search, step, mesh, kind};
+}
+// ... and the one a launch with these parameters runs as kernel kind `kind`;
+// corner: the corner records are passed (launch_trace)
+inline TraceVariant trace_variant(const TraceParams &p, bool corner, int kind) {
+    const int mesh = trace_mesh_kind(p.ntri != 0, p.tnodes != 0);
+    const int search = !p.nnodes ? kSearchBrute : !p.use_lds ? kSearchGlobal : corner ? kSearchLdsCorner : kSearchLdsBox;
+    return trace_variant(search, p.step != 0, mesh == 2 && p.tw_nodes != nullptr ? 3 : mesh, kind);
+}
+// Frames rendered without stats run a kind whose work counters compile away
+// (one VALU increment per node / sphere test / ray); SERIAL passes their own.
+inline TraceVariant trace_variant(const TraceParams &p, bool corner) {
+    return trace_variant(p, corner, p.mode >= kRngSerialCount ? kKindSerial : p.stats ? kKindCounting : kKindLean);
+}
+
 // corner (sphere-only frames with p.use_lds): the corner records (bvh.h
 // SphereBVH::corner, 8 uint4 per node) the workgroups stage instead of the box
-// records (the corner-record kernel instances; trace_corner_lds bytes each)
+// records (the corner-record kernel instances; trace_corner_lds bytes each).
+// Runs instance trace_variant(p, corner != nullptr).
 hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream,
                         const uint4 *corner = nullptr);
 // Primary sphere lists built on the device (bvh.h build_primary_sphere_lists,
@@ -344,18 +386,9 @@ hipError_t launch_resolve_ex(const float *samples, uint32_t *out, uint32_t npix,
 hipError_t launch_assemble(const uint32_t *gathered, uint32_t *out, uint32_t width, uint32_t height,
                            uint32_t row_block, uint32_t nranks, uint32_t max_rows,
                            hipStream_t stream);
-// variant: 0 brute force, 1 BVH from global memory, 2 BVH staged in LDS, 3 the
-// corner-record instances (mesh 0, kinds 0 and 1);
-// step: the sliced-walk kernel (TraceParams::step); mesh: trace_mesh_kind
-// workgroups per CU of one trace_kernel instance (kind: 0 the lean frame
-// kernel, 1 the counting frame kernel, 2 the SERIAL passes)
-hipError_t trace_occupancy(int *blocks_per_cu, int variant, size_t lds_bytes, bool step, int mesh,
-                           int kind);
-// The kernel family of a scene: 0 no triangles, 1 triangles searched by brute
-// force (no triangle tree), 2 triangle trees (TraceParams::tnodes != 0)
-inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : tree ? 2 : 1; }
-// kMesh 3: kind 2 walked through the 4-wide image (TraceParams::tw_nodes); the
-// SERIAL passes keep the binary walk
+// workgroups per CU of one instance with lds_bytes of dynamic LDS
+// (hipErrorInvalidValue: no such instance)
+hipError_t trace_occupancy(int *blocks_per_cu, TraceVariant v, size_t lds_bytes);
 size_t trace_lds_bytes(const TraceParams &p, bool corner = false);
 // the sphere tree's LDS copy (render.hip stage_tree)
 __host__ __device__ inline size_t trace_tree_lds(uint32_t nnodes, uint32_t nprims, uint32_t nsph_padded) {
@@ -377,11 +410,11 @@ constexpr size_t kLdsPerCu = 160 * 1024, kLdsDefaultMax = 64 * 1024;
 hipError_t trace_lds_opt_in();
 // the LDS copy addresses its 64-B node records with u16 byte addresses (0xFFFF: end)
 constexpr uint32_t kLdsTreeMaxNodes = 1023;
-// threads per trace workgroup: LDS-tree kernels (per kernel family, trace_mesh_kind
-// or 3 for the wide walk) vs global
-uint32_t trace_block_threads(bool lds, int mesh, int kind);
-// dynamic LDS of one trace workgroup: the sphere tree (lds) and, for the wide
-// triangle walk, every lane's stack (u16 entries)
-size_t trace_dyn_lds(const TraceParams &p, bool lds, bool wide, uint32_t threads, bool corner = false);
+// threads per workgroup of an instance (LDS-tree kernels: per family and kind;
+// the others 256)
+uint32_t trace_block_threads(TraceVariant v);
+// dynamic LDS of one trace workgroup: the sphere tree (LDS searches) and, for
+// the wide triangle walk, every lane's stack (u16 entries)
+size_t trace_dyn_lds(const TraceParams &p, TraceVariant v);
 
 }  // namespace rtamd

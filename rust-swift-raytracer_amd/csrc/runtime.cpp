@@ -119,21 +119,24 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
         const TriangleBVH &tw = w.tbvh;
         const uint32_t tw_depth = std::max<uint32_t>(1u, 3u * std::max(tw.wdepth, w.tcells.wdepth));
         bool wide = !tw.wnodes.empty() && env_u64("RT_AMD_TRI_WIDE", 1) != 0 &&
-                    (size_t)tw_depth * trace_block_threads(true, 3, 0) * 2u <= 64u * 1024u;
+                    (size_t)tw_depth * trace_block_threads(trace_variant(kSearchLdsBox, false, 3, kKindLean)) * 2u <=
+                        64u * 1024u;
         int tri = wide ? 3 : trace_mesh_kind(w.packed.ntri > 0, !w.tbvh.nodes.empty());
-        // the stack's LDS (kinds 0 and 1: SERIAL passes keep the binary walk)
-        auto stack_lds = [&](int c, uint32_t threads) -> size_t {
-            return tri == 3 && c != 2 ? (size_t)tw_depth * threads * 2u : 0u;
+        // the instance of kind c this scene runs with sphere search `search`
+        auto variant = [&](int search, int st, int c) { return trace_variant(search, st != 0, tri, c); };
+        // the wide walk's stacks in LDS
+        auto stack_lds = [&](TraceVariant v) -> size_t {
+            return v.mesh == 3 ? (size_t)tw_depth * trace_block_threads(v) * 2u : 0u;
         };
         // workgroups per CU of the kernels without the LDS sphere tree
         auto occupancy_global = [&]() -> hipError_t {
             for (int c = 0; c < 3; ++c)
-                for (int st = 0; st < 2; ++st) {
-                    hipError_t e = trace_occupancy(&d->blocks_per_cu[c][st], 0, stack_lds(c, 256), st, tri, c);
-                    if (e == hipSuccess)
-                        e = trace_occupancy(&d->blocks_per_cu_bvh[c][st], 1, stack_lds(c, 256), st, tri, c);
-                    if (e != hipSuccess) return e;
-                }
+                for (int st = 0; st < 2; ++st)
+                    for (int search : {kSearchBrute, kSearchGlobal}) {
+                        const TraceVariant v = variant(search, st, c);
+                        const hipError_t e = trace_occupancy(&d->occupancy(v), v, stack_lds(v));
+                        if (e != hipSuccess) return e;
+                    }
             return hipSuccess;
         };
         // LDS trees above 64 KB per workgroup need the kernels' opt-in, before
@@ -194,16 +197,15 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
             // CU it has at 64 KB (the lean sphere kernel: 2 x 1024 threads, i.e.
             // 80 KB each; losing one costs far more than the LDS walk saves).
             // bytes: the workgroup's whole request; with the wide triangle
-            // walk's stacks in it (stacks) the 64 KB rule stays as it was.
-            // variant: trace_occupancy's (2 box records, 3 corner records)
-            auto keeps_workgroups = [&](int blocks, size_t bytes, bool stacks, int variant, int st, int mesh,
-                                        int c, bool &ok) -> hipError_t {
+            // walk's stacks in it (mesh 3) the 64 KB rule stays as it was.
+            auto keeps_workgroups = [&](TraceVariant v, size_t bytes, bool &ok) -> hipError_t {
+                const int blocks = d->occupancy(v);
                 ok = blocks > 0;
                 if (!ok || bytes <= kLdsDefaultMax) return hipSuccess;
                 ok = false;
-                if (stacks) return hipSuccess;
+                if (v.mesh == 3) return hipSuccess;
                 int ref = 0;
-                const hipError_t e = trace_occupancy(&ref, variant, kLdsDefaultMax, st, mesh, c);
+                const hipError_t e = trace_occupancy(&ref, v, kLdsDefaultMax);
                 ok = e == hipSuccess && blocks == ref;
                 return e;
             };
@@ -216,9 +218,9 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
                 for (int c = 0; c < 2 && fits; ++c)
                     for (int st = 0; st < 2 && fits; ++st) {
                         // (a query the runtime refuses: the layout does not fit)
-                        if (trace_occupancy(&d->blocks_per_cu_corner[c][st], 3, corner, st, 0, c) != hipSuccess ||
-                            keeps_workgroups(d->blocks_per_cu_corner[c][st], corner, false, 3, st, 0, c, fits) !=
-                                hipSuccess) {
+                        const TraceVariant v = variant(kSearchLdsCorner, st, c);
+                        if (trace_occupancy(&d->occupancy(v), v, corner) != hipSuccess ||
+                            keeps_workgroups(v, corner, fits) != hipSuccess) {
                             (void)hipGetLastError();
                             fits = false;
                         }
@@ -245,15 +247,13 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
                     fits = true;
                     for (int c = 0; c < 3; ++c)
                         for (int st = 0; st < 2; ++st) {
-                            const uint32_t lt = trace_block_threads(true, tri == 3 && c == 2 ? 2 : tri, c);
-                            const size_t sb = stack_lds(c, lt);
+                            const TraceVariant v = variant(kSearchLdsBox, st, c);
+                            const size_t sb = stack_lds(v);
                             const size_t total = sb ? ((lds + 15u) & ~(size_t)15u) + sb : lds;
-                            const hipError_t e = trace_occupancy(&d->blocks_per_cu_lds[c][st], 2, total, st, tri, c);
+                            const hipError_t e = trace_occupancy(&d->occupancy(v), v, total);
                             if (e != hipSuccess) return e;
                             bool ok = false;
-                            if (keeps_workgroups(d->blocks_per_cu_lds[c][st], total, sb != 0, 2, st, tri, c, ok) !=
-                                hipSuccess)
-                                (void)hipGetLastError();
+                            if (keeps_workgroups(v, total, ok) != hipSuccess) (void)hipGetLastError();
                             fits = fits && ok;
                         }
                     return hipSuccess;
@@ -303,10 +303,10 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
         for (int c = 0; c < 3; ++c)
             for (int st = 0; st < 2; ++st) {
                 if (bpc)
-                    d->blocks_per_cu[c][st] = d->blocks_per_cu_bvh[c][st] = d->blocks_per_cu_lds[c][st] =
-                        (int)bpc;
-                d->blocks_per_cu[c][st] = std::max(d->blocks_per_cu[c][st], 1);
-                d->blocks_per_cu_bvh[c][st] = std::max(d->blocks_per_cu_bvh[c][st], 1);
+                    for (int search : {kSearchBrute, kSearchGlobal, kSearchLdsBox})
+                        d->blocks_per_cu[search][c][st] = (int)bpc;
+                for (int search : {kSearchBrute, kSearchGlobal})
+                    d->blocks_per_cu[search][c][st] = std::max(d->blocks_per_cu[search][c][st], 1);
             }
         HIP_TRY(hipMalloc((void **)&d->counter, 2 * kMaxParts * 128));
         slot = std::move(d);
@@ -704,18 +704,12 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         1, env_u64("RT_AMD_REFILL", wide_frame ? 16 : p.step ? 1 : 24));
     p.walk_min = (uint32_t)env_u64("RT_AMD_WALK_MIN", 65);  // sphere-only: walk when nothing else can advance
     p.tri_walk_min = (uint32_t)env_u64("RT_AMD_TRI_WALK_MIN", wide_frame ? 64 : 32);
-    const int sv = p.step ? 1 : 0;
     const bool timed = stats != nullptr;  // HIP-event timing + counters need a host wait
-    // launch_trace runs the counting variant iff p.stats, the SERIAL instances for sp
-    const int ctv = sp ? 2 : timed ? 1 : 0;
-    const int bpc = !use_bvh   ? d->blocks_per_cu[ctv][sv]
-                    : corner_img ? d->blocks_per_cu_corner[ctv][sv]
-                    : p.use_lds ? d->blocks_per_cu_lds[ctv][sv]
-                                : d->blocks_per_cu_bvh[ctv][sv];
-    // (the kernel family launch_trace picks: the wide triangle walk for frames)
-    const int fam = p.ntri == 0 ? 0 : p.tnodes == 0 ? 1 : (p.tw_nodes != nullptr && ctv != 2) ? 3 : 2;
-    const uint64_t waves_per_block = trace_block_threads(use_bvh && p.use_lds, fam, ctv) / 64;
-    const uint64_t full_blocks = (uint64_t)bpc * (uint64_t)d->num_cus;
+    // launch_trace runs the counting kind iff p.stats (set below), the SERIAL instances for sp
+    const int ctv = sp ? kKindSerial : timed ? kKindCounting : kKindLean;
+    const TraceVariant tv = trace_variant(p, corner_img != nullptr, ctv);
+    const uint64_t waves_per_block = trace_block_threads(tv) / 64;
+    const uint64_t full_blocks = (uint64_t)d->occupancy(tv) * (uint64_t)d->num_cus;
     uint32_t launches = 0, waves = 0;
     // counters only when asked for: one 16-slot record per wave, summed here
     const uint64_t max_waves = full_blocks * waves_per_block;
@@ -800,13 +794,11 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // workgroups, waves, jobs per queue pull (chunk) and job-queue partitions
     struct LaunchPlan { uint64_t blocks, nwaves, chunk, parts, block_threads; };
     auto plan = [&](int k, uint64_t njobs) -> LaunchPlan {
-        const int kb = !use_bvh    ? d->blocks_per_cu[k][sv]
-                       : corner_img ? d->blocks_per_cu_corner[k][sv]
-                       : p.use_lds ? d->blocks_per_cu_lds[k][sv]
-                                   : d->blocks_per_cu_bvh[k][sv];
-        const uint64_t wpb = trace_block_threads(use_bvh && p.use_lds, fam, k) / 64;
+        const TraceVariant v = trace_variant(p, corner_img != nullptr, k);
+        const uint64_t wpb = trace_block_threads(v) / 64;
         const uint64_t jobs_per_block = wpb * 256;
-        uint64_t blocks = std::min<uint64_t>((uint64_t)kb * d->num_cus, (njobs + jobs_per_block - 1) / jobs_per_block);
+        uint64_t blocks = std::min<uint64_t>((uint64_t)d->occupancy(v) * d->num_cus,
+                                             (njobs + jobs_per_block - 1) / jobs_per_block);
         blocks = std::max<uint64_t>(blocks, 1);
         const uint64_t nwaves = blocks * wpb;
         uint64_t chunk = env_u64("RT_AMD_CHUNK", 0);
@@ -949,8 +941,8 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     fx.launch_wsteps = p.wsteps;
     fx.launch_block_threads = (uint32_t)lean_plan.block_threads;
     fx.launch_blocks = (uint32_t)lean_plan.blocks;
-    fx.sphere_tree = !use_bvh ? 0u : !p.use_lds ? 1u : corner_img ? 3u : 2u;
-    fx.sphere_tree_lds_bytes = use_bvh && p.use_lds ? (uint32_t)trace_lds_bytes(p, corner_img != nullptr) : 0u;
+    fx.sphere_tree = (uint32_t)tv.search;
+    fx.sphere_tree_lds_bytes = tv.lds() ? (uint32_t)trace_lds_bytes(p, tv.search == kSearchLdsCorner) : 0u;
     fx.nsph = d->nsph;
     fx.ntri = d->ntri;
     fx.nbig = d->nbig;

@@ -65,7 +65,7 @@ struct DeviceState {
     uint64_t ptl_version = 0;
     uint2 *spl = nullptr;                                       // primary sphere lists
     uint64_t spl_version = 0;
-    // primary sphere lists built on the device (render.hip launch_sphere_lists)
+    // primary sphere lists built on the device (serial.hip launch_sphere_lists)
     uint2 *gspl = nullptr;           size_t gspl_cap = 0;
     int4 *gspl_rects = nullptr;      size_t gspl_rects_cap = 0;
     uint32_t *gspl_flag = nullptr;   size_t gspl_flag_cap = 0;
@@ -77,7 +77,6 @@ struct DeviceState {
     // frame kernels can stage them without losing a workgroup per CU
     uint4 *bvh_corner = nullptr;
     size_t corner_bytes = 0;                                   // 0: box records (or no LDS tree)
-    int blocks_per_cu_corner[2][2] = {};                       // [lean, counting][step]
     float *samples = nullptr;        size_t samples_cap = 0;   // sample slab (3 planes)
     float *ring = nullptr;           size_t ring_cap = 0;      // per-wave sample rings (fused resolve)
     uint32_t *out = nullptr;         size_t out_cap = 0;       // RGBA8 tile (host path)
@@ -108,9 +107,11 @@ struct DeviceState {
     uint32_t cset = 0;              // the set the next frame launch uses ...
     bool cset_clean[2] = {false, false};  // ... and whether each set is known to be zero
     unsigned long long *stats = nullptr; size_t stats_cap = 0;  // per-wave counter records
-    // resident workgroups per CU of each kernel variant, [0]: whole walks, [1]: sliced walks
-    // [count][step]: workgroups per CU of each kernel instance
-    int blocks_per_cu[3][2] = {}, blocks_per_cu_bvh[3][2] = {}, blocks_per_cu_lds[3][2] = {};
+    // resident workgroups per CU of the scene's kernel instances (render.h
+    // TraceVariant), [search][kind][step], queried once at device setup for the
+    // scene's family (the corner search: frame kinds only)
+    int blocks_per_cu[4][3][2] = {};
+    int &occupancy(TraceVariant v) { return blocks_per_cu[v.search][v.kind][v.step]; }
     int num_cus = 0;
     // a counted frame's timing events (3 per launch: start, trace end, resolve
     // end) and its wave records copied to pinned host memory; with

@@ -10,7 +10,10 @@ false>), i.e. the bytes of each such function symbol plus its kernel
 descriptor (less its position-dependent code-entry offset), taken from the
 clang offload bundle in the .hip_fatbin section.
 
-  python tools/kernel_hash.py [lib.so]      -> prints the hash and the symbols
+  python tools/kernel_hash.py [lib.so]        -> prints the hash and the symbols
+  python tools/kernel_hash.py --all [lib.so]  -> one sha256 per gfx950 kernel of the
+      library (code + descriptor, as above), sorted by name: two builds hold
+      the same device code iff `diff` finds the two listings equal
 """
 import hashlib
 import os
@@ -63,34 +66,59 @@ def _elf_symbols(elf):
     return out
 
 
-def frame_kernel_hash(lib=LIB):
-    """(sha256 hex, [symbol names]) of the lean frame trace kernels, or (None, [])."""
+def _gfx950_symbols(lib):
     with open(lib, "rb") as fh:
         blob = fh.read()
     syms = {}
     for triple, code in _bundles(blob):
         if "gfx950" in triple:
             syms.update(_elf_symbols(code))
+    return syms
+
+
+def _update(h, syms, n):
+    h.update(n.encode())
+    h.update(syms[n])
+    # the kernel descriptor (register counts, LDS / scratch / kernarg sizes)
+    # without kernel_code_entry_byte_offset (bytes 16-23): that field is the
+    # distance from the descriptor to the code, which moves whenever any
+    # other kernel of the library changes size
+    kd = bytearray(syms.get(n + ".kd", b""))
+    if len(kd) >= 24:
+        kd[16:24] = bytes(8)
+    h.update(bytes(kd))
+
+
+def frame_kernel_hash(lib=LIB):
+    """(sha256 hex, [symbol names]) of the lean frame trace kernels, or (None, [])."""
+    syms = _gfx950_symbols(lib)
     names = sorted(n for n in syms if "trace_kernel" in n and n.endswith(FRAME_SUFFIX))
     if not names:
         return None, []
     h = hashlib.sha256()
     for n in names:
-        h.update(n.encode())
-        h.update(syms[n])
-        # the kernel descriptor (register counts, LDS / scratch / kernarg sizes)
-        # without kernel_code_entry_byte_offset (bytes 16-23): that field is the
-        # distance from the descriptor to the code, which moves whenever any
-        # other kernel of the library changes size
-        kd = bytearray(syms.get(n + ".kd", b""))
-        if len(kd) >= 24:
-            kd[16:24] = bytes(8)
-        h.update(bytes(kd))
+        _update(h, syms, n)
     return h.hexdigest(), names
 
 
+def all_kernel_hashes(lib=LIB):
+    """[(kernel symbol, sha256 hex)] of every gfx950 kernel, sorted by name."""
+    syms = _gfx950_symbols(lib)
+    out = []
+    for n in sorted(n for n in syms if n + ".kd" in syms):
+        h = hashlib.sha256()
+        _update(h, syms, n)
+        out.append((n, h.hexdigest()))
+    return out
+
+
 if __name__ == "__main__":
-    digest, names = frame_kernel_hash(sys.argv[1] if len(sys.argv) > 1 else LIB)
+    args = [a for a in sys.argv[1:] if a != "--all"]
+    if "--all" in sys.argv[1:]:
+        for n, digest in all_kernel_hashes(args[0] if args else LIB):
+            print(digest, n)
+        sys.exit(0)
+    digest, names = frame_kernel_hash(args[0] if args else LIB)
     print(digest)
     for n in names:
         print("  ", n)
