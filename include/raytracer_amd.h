@@ -181,6 +181,78 @@ int rt_render_device(const Rust_WorldHandle *handle, size_t width, size_t height
                      const RtRenderOptions *opts, void *d_rgba, void *hip_stream,
                      RtRenderStats *stats);
 
+/* Progressive accumulation: refine a frame pass by pass.
+ *
+ * An accumulator is a device-resident per-pixel f32 sum of sample colours for
+ * one world, one frame size and the handle's camera, on one device (whole
+ * frames: no row tiles, no ndevices).  It is created with a sample stride S,
+ * the most samples per pixel it will ever hold.  Sample s (0 <= s < S) of the
+ * pixel at reference (row, col), row 0 = bottom, is global job
+ * g = (row*width + col)*S + s: in COUNTER mode it starts xorshift32 from
+ * rt_sample_seed(seed, g), in REPLAY mode from replay_states[g]; inside a
+ * sample everything is the frame's trace.  With N0 samples held, a pass of n
+ * traces samples N0 .. N0+n-1 of every pixel, continues each pixel's three
+ * sums in sample order (the reference's fold, common.rs:333-341, stopped and
+ * continued from the stored f32 sum: the same bits as a fold that never
+ * stopped) and writes the RGBA8 frame of N = N0 + n samples,
+ * sqrt(sum * (1/(N as f32))) * 255.999 as u8 per channel.  So after passes
+ * totalling S the frame is bit-identical to rt_render_ex at
+ * samples_per_pixel = S in the same mode, whatever the split.
+ *
+ * The accumulator resets itself to N = 0 when the handle's camera (its 12
+ * floats) differs from the one the held samples were traced with, and when the
+ * scene was edited (rt_world_set_*_material): a viewer's loop is "move, add,
+ * show".  RT_RNG_SERIAL is rejected (one stream over the whole frame has no
+ * per-pass meaning).  A pass that would exceed S, or nsamples <= 0, is an
+ * error and traces nothing.  Requests above 4096 samples run as consecutive
+ * passes inside the call.
+ *
+ * Ownership: free the accumulator before its world.  After rt_free_world
+ * every call on the accumulator but rt_accum_free fails with an error (it
+ * does not touch the freed handle).  Calls on one handle's accumulators and
+ * frames are serialised by the handle's lock. */
+typedef struct RtAccum RtAccum;
+
+typedef struct RtAccumOptions {
+  int32_t max_ray_bounces;        /* as RtRenderOptions                          */
+  uint32_t rng_mode;              /* RT_RNG_COUNTER or RT_RNG_REPLAY             */
+  uint32_t seed;                  /* COUNTER base seed                           */
+  const uint32_t *replay_states;  /* REPLAY: host table of width*height*S u32,
+                                     index (row*width + col)*S + s, row 0 =
+                                     bottom; uploaded once by rt_accum_create   */
+  uint32_t sample_stride;         /* S >= 1                                      */
+  int32_t device;                 /* HIP device ordinal, -1 = current device     */
+  int32_t accel;                  /* RT_ACCEL_*                                  */
+} RtAccumOptions;
+
+/* depth 8, COUNTER, seed 2547549, sample_stride 64, device -1, RT_ACCEL_AUTO. */
+void rt_accum_default_options(RtAccumOptions *opts);
+/* NULL on error (rt_last_error); opts NULL = the defaults. */
+RtAccum *rt_accum_create(const Rust_WorldHandle *handle, size_t width, size_t height,
+                         const RtAccumOptions *opts);
+/* Adds nsamples per pixel and writes the frame of all held samples to host
+ * `pixels` (width*height RGBA8, top row first; NULL: accumulate only).
+ * Synchronous when pixels or stats is given.  Stats of a pass fill samples,
+ * trace_ms, trace_launches (summed over the call's passes), waves,
+ * fused_resolve, accel, sphere_tree* and launch_*; the work counters (rays,
+ * sphere_tests, tri_*, bvh_*, big_sphere_tests) stay 0: accumulation has no
+ * counting kernel.  Returns 0 or a negative error. */
+int rt_accum_add(RtAccum *acc, int64_t nsamples, Rust_ColorU8 *pixels, RtRenderStats *stats);
+/* Same, the frame to DEVICE memory d_rgba (NULL: accumulate only) on
+ * hip_stream (NULL = the library's stream).  With stats == NULL the pass is
+ * only enqueued (no host wait), like rt_render_device. */
+int rt_accum_add_device(RtAccum *acc, int64_t nsamples, void *d_rgba, void *hip_stream,
+                        RtRenderStats *stats);
+/* Samples per pixel held (0 after a reset, also one that the next add would
+ * make: a moved camera or an edited scene), or a negative error. */
+long rt_accum_samples(RtAccum *acc);
+/* The raw sums: width*height*3 f32, top row first, RGB interleaved (all 0.0
+ * with no samples held).  Waits for the last pass.  0 or a negative error. */
+int rt_accum_read(RtAccum *acc, float *sums);
+/* Forgets the held samples (the next pass starts from zero sums). */
+int rt_accum_reset(RtAccum *acc);
+void rt_accum_free(RtAccum *acc);
+
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).
  * That launch must have been rendered with RT_FLAG_KEEP_SAMPLES.  Output

@@ -21,6 +21,12 @@ struct Rust_World {
 struct Rust_Camera {
     rtamd::CameraModel cam;
 };
+// The handle is read at every call (callers replace handle->camera), never
+// after its world was freed (state->world is nullptr then).
+struct RtAccum {
+    const Rust_WorldHandle *handle;
+    rtamd::AccumState *state;
+};
 
 namespace {
 thread_local int g_parse_status = rtamd::kParseOk;
@@ -242,6 +248,7 @@ static int set_material(Rust_WorldHandle *h, bool tri, size_t i, const float *m)
     sc.materials[idx] = rtamd::Material{(uint32_t)k, m[1], m[2], m[3], m[4], m[5]};
     w.packed = rtamd::pack_scene(sc, 8, 1);
     w.devices.clear();  // the next frame uploads the scene again
+    ++w.edit_version;   // (accumulators start over)
     return 0;
 }
 
@@ -300,6 +307,81 @@ int rt_assemble_tiles(const void *d_gathered, void *d_out, size_t width, size_t 
                       uint32_t nranks, size_t max_rows, void *hip_stream) {
     return rtamd::assemble_tiles(static_cast<const uint32_t *>(d_gathered), static_cast<uint32_t *>(d_out), width,
                                  height, row_block, nranks, max_rows, static_cast<hipStream_t>(hip_stream));
+}
+
+// ---- progressive accumulation
+void rt_accum_default_options(RtAccumOptions *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->max_ray_bounces = 8;       // lib.rs:51
+    o->rng_mode = RT_RNG_COUNTER;
+    o->seed = 2547549u;           // random.rs:9
+    o->sample_stride = 64;
+    o->device = -1;
+    o->accel = RT_ACCEL_AUTO;
+}
+
+RtAccum *rt_accum_create(const Rust_WorldHandle *h, size_t width, size_t height, const RtAccumOptions *opts) {
+    if (!h || !h->world || !h->camera) {
+        rtamd::set_error("rt_accum_create: null world handle");
+        return nullptr;
+    }
+    RtAccumOptions o;
+    if (opts) o = *opts;
+    else rt_accum_default_options(&o);
+    rtamd::AccumState *st = rtamd::accum_create(h->world->state, width, height, o.sample_stride, o.max_ray_bounces,
+                                                o.rng_mode, o.seed, o.replay_states, o.device, o.accel);
+    return st ? new RtAccum{h, st} : nullptr;
+}
+
+// the accumulator's current camera, or nullptr (with the error set)
+static const rtamd::CameraModel *accum_camera(const RtAccum *acc, const char *who) {
+    if (!acc || !acc->state) {
+        rtamd::set_error(std::string(who) + ": null accumulator");
+        return nullptr;
+    }
+    if (!acc->state->world) {
+        rtamd::set_error(std::string(who) + ": the accumulator's world was freed");
+        return nullptr;
+    }
+    if (!acc->handle->camera) {
+        rtamd::set_error(std::string(who) + ": null camera");
+        return nullptr;
+    }
+    return &acc->handle->camera->cam;
+}
+
+int rt_accum_add(RtAccum *acc, int64_t nsamples, Rust_ColorU8 *pixels, RtRenderStats *stats) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_add");
+    if (!cam) return -1;
+    return rtamd::accum_add(*acc->state, *cam, nsamples, nullptr, nullptr, pixels, stats);
+}
+
+int rt_accum_add_device(RtAccum *acc, int64_t nsamples, void *d_rgba, void *hip_stream, RtRenderStats *stats) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_add_device");
+    if (!cam) return -1;
+    return rtamd::accum_add(*acc->state, *cam, nsamples, static_cast<uint32_t *>(d_rgba),
+                            static_cast<hipStream_t>(hip_stream), nullptr, stats);
+}
+
+long rt_accum_samples(RtAccum *acc) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_samples");
+    return cam ? rtamd::accum_samples(*acc->state, *cam) : -1;
+}
+
+int rt_accum_read(RtAccum *acc, float *sums) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_read");
+    return cam ? rtamd::accum_read(*acc->state, *cam, sums) : -1;
+}
+
+int rt_accum_reset(RtAccum *acc) {
+    if (!accum_camera(acc, "rt_accum_reset")) return -1;
+    return rtamd::accum_reset(*acc->state);
+}
+
+void rt_accum_free(RtAccum *acc) {
+    if (!acc) return;
+    rtamd::accum_free(acc->state);
+    delete acc;
 }
 
 int rt_device_count(void) {

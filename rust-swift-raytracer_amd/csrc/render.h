@@ -214,9 +214,10 @@ inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : 
 //   step:   the sliced-walk kernel (TraceParams::step)
 //   mesh:   trace_mesh_kind, or 3: triangle trees walked through the 4-wide
 //           image (TraceParams::tw_nodes)
-//   kind:   what the jobs are
+//   kind:   what the jobs are (kKindAccum: one pass of a progressive
+//           accumulation, launch_trace_accum; lean-like, no counters)
 enum : int { kSearchBrute = 0, kSearchGlobal = 1, kSearchLdsBox = 2, kSearchLdsCorner = 3 };
-enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2 };
+enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2, kKindAccum = 3 };
 struct TraceVariant {
     int search;
     bool step;
@@ -251,6 +252,20 @@ inline TraceVariant trace_variant(const TraceParams &p, bool corner) {
 // Runs instance trace_variant(p, corner != nullptr).
 hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream,
                         const uint4 *corner = nullptr);
+// One pass of a progressive accumulation: the frame launch p
+// (p.spp = the pass's samples per pixel n, fused resolve, one rank) as instance
+// trace_variant(p, corner != nullptr, kKindAccum).  Sample s of the pass at
+// reference (row, col) is global job (row W + col) stride + n0 + s (seed /
+// replay index; 32-bit arithmetic when p.gj32, which the host sets iff
+// W H stride < 2^32).  sums: three f32 planes of W H sums (R, G, B), indexed
+// like p.out: each pixel's fold starts from its stored sum and the new sum is
+// stored back before gamma (p.inv_spp and p.alpha_u8 are those of n0 + n samples).
+struct AccumTail {
+    float *sums;
+    uint32_t n0, stride;
+};
+hipError_t launch_trace_accum(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
+                              const AccumTail &tail);
 // Primary sphere lists built on the device (bvh.h build_primary_sphere_lists,
 // the same double arithmetic per sphere, then one thread per pixel collecting
 // the spheres whose projected box covers it, in tree order): rec gets 2 u32

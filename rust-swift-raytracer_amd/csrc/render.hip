@@ -873,10 +873,21 @@ __device__ __forceinline__ void resolve_store(const TraceParams &p, uint32_t lp,
 // wide triangle walk (A/B on C5, 1-pixel chunks: 149.8 -> 148.1 ms, 2 VGPRs
 // spilled); the binary triangle walk keeps one lane per pixel
 #define RT_PLANE_LANES(mesh) ((mesh) < 2 || (mesh) == 3)
-template <bool kPlaneLanes>
+// kAccum (accumulation passes, render.h AccumTail): a pixel's fold starts from
+// its stored sum (sums: three planes of width * height floats, indexed like
+// p.out) instead of 0.0f and the new sum is stored back before gamma -- the
+// f32 fold of common.rs:333-341 stopped after a sample and continued from the
+// stored sum is the fold that never stopped.  A pixel belongs to one chunk of
+// one wave per pass, so nothing else touches its three sums.
+__device__ __forceinline__ size_t resolve_index(const TraceParams &p, uint32_t lp) {
+    const uint32_t q = fdiv(lp, p.div_width);
+    const uint32_t col = lp - q * p.width;
+    return (size_t)(p.slab_row0 + q) * p.width + col;
+}
+template <bool kPlaneLanes, bool kAccum = false>
 __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float *ring, uint32_t plane,
                                               uint32_t off, uint32_t base, uint32_t len,
-                                              uint32_t lane) {
+                                              uint32_t lane, float *sums = nullptr) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const uint32_t spp = p.spp;
@@ -887,6 +898,11 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
         const bool on = lane < 3u * np;
         const float *src = ring + off + c * plane + (on ? g : 0u) * spp;
         float acc = 0.0f;
+        float *held = nullptr;  // (kAccum) the lane's plane sum
+        if (kAccum) {
+            held = sums + (size_t)c * ((size_t)p.width * p.height) + resolve_index(p, pix0 + (on ? g : 0u));
+            if (on) acc = *held;
+        }
         for (uint32_t k = 0; k < spp; k += 16u) {
             float4 v[4];
 #pragma unroll
@@ -907,6 +923,7 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
         // gamma + `as u8` of the lane's own plane sum (resolve_store's
         // operations on the same value: the same byte), one pass for the
         // three planes; the pixel's lane then collects the G and B bytes
+        if (kAccum && on) *held = acc;
         const uint32_t ch = resolve_channel(p, acc);
         const uint32_t G = (uint32_t)__shfl((int)ch, (int)(lane < np ? np + lane : lane));
         const uint32_t B = (uint32_t)__shfl((int)ch, (int)(lane < np ? 2u * np + lane : lane));
@@ -916,10 +933,23 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
     for (uint32_t i = lane; i < np; i += kWave) {
         const float *src = ring + off + i * spp;
         float r = 0.0f, g = 0.0f, b = 0.0f;
+        float *held = nullptr;  // (kAccum) the pixel's R sum; G and B a plane further each
+        const size_t hplane = kAccum ? (size_t)p.width * p.height : 0u;
+        if (kAccum) {
+            held = sums + resolve_index(p, pix0 + i);
+            r = held[0];
+            g = held[hplane];
+            b = held[2 * hplane];
+        }
         for (uint32_t k = 0; k < spp; ++k) {
             r = r + src[k];
             g = g + src[plane + k];
             b = b + src[2 * plane + k];
+        }
+        if (kAccum) {
+            held[0] = r;
+            held[hplane] = g;
+            held[2 * hplane] = b;
         }
         resolve_store(p, pix0 + i, r, g, b);
     }
@@ -1081,8 +1111,20 @@ constexpr int trace_waves_per_eu(bool lds, int mesh, int kind) {
 }
 // kCorner: the LDS tree is the corner-record image `corner` (sphere-only frame
 // kernels, corner::trace_kernel below); every other instance is trace_kernel.
-template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner>
-__device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
+// kAccum: one pass of a progressive accumulation (accum::trace_kernel below):
+// the refill's global job and the chunk resolve's fold read `tail`.
+// The accumulation kernels' argument block: it begins with the TraceParams
+// (kargs() re-reads them from offset 0; TraceParams itself gets no field, its
+// offsets are those the frame kernels' kernarg loads were tuned with), then
+// the corner image (nullptr for the other searches) and the tail.
+struct AccumParams {
+    TraceParams p;
+    const uint4 *image;
+    AccumTail tail;
+};
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner,
+          bool kAccum = false>
+__device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, AccumTail tail = AccumTail{}) {
     // SERIAL count passes: the walk of the previous pass set the first sample
     // and this iteration's candidates per sample (ctrl[5], <= the launch's K)
     if (kSerial && p.ctrl != nullptr) {
@@ -1136,6 +1178,17 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
         return *(const TraceParams *)kp;
 #else
         return p;
+#endif
+    };
+    // (kAccum) the tail of the argument block, re-read the same way
+    auto atail = [&]() -> const AccumTail & {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_NO_KARG_RELOAD)
+        const __attribute__((address_space(4))) AccumParams *kp =
+            (const __attribute__((address_space(4))) AccumParams *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));
+        return ((const AccumParams *)kp)->tail;
+#else
+        return tail;
 #endif
     };
     extern __shared__ float4 lds[];
@@ -1699,7 +1752,10 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     rleft[k] -= n;
                     if (n != 0 && rleft[k] == 0) {
                         const TraceParams &pc = kargs();
-                        if (!(pc.ablate & 2u))
+                        if (kAccum)
+                            resolve_chunk<RT_PLANE_LANES(kMesh), true>(pc, sbase, pstride, k << pc.ring_shift,
+                                                                       rbase[k], rlen[k], lane, atail().sums);
+                        else if (!(pc.ablate & 2u))
                             resolve_chunk<RT_PLANE_LANES(kMesh)>(pc, sbase, pstride, k << pc.ring_shift, rbase[k],
                                                   rlen[k], lane);
                         rfree |= 1u << k;
@@ -1800,7 +1856,19 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                 // enumeration order changes no bits.
                 uint32_t s, col, row;
                 uint64_t gjob = 0;
-                if (!kSerial && pc.gj32) {
+                if (kAccum) {
+                    // sample N0 + s of the pixel, its job at the accumulator's
+                    // sample stride (whole frames of one rank: tile row = image row)
+                    const AccumTail &t = atail();
+                    const uint32_t lp = fdiv(job, pc.div_spp);
+                    const uint32_t q = fdiv(lp, pc.div_width);
+                    s = job - lp * pc.spp;
+                    col = lp - q * pc.width;
+                    row = pc.height - 1u - (pc.slab_row0 + q);
+                    const uint32_t pix = row * pc.width + col;
+                    if (pc.gj32) gjob = pix * t.stride + (t.n0 + s);  // (W H S < 2^32)
+                    else gjob = (uint64_t)pix * t.stride + (t.n0 + s);
+                } else if (!kSerial && pc.gj32) {
                     // one rank, 32-bit global jobs (TraceParams::gj32)
                     const uint32_t lp = fdiv(job, pc.div_spp);
                     const uint32_t q = fdiv(lp, pc.div_width);
@@ -1932,6 +2000,22 @@ void trace_kernel(CornerParams c) {
 }
 }  // namespace corner
 
+// Accumulation passes (kKindAccum): the lean frame kernels' twins with
+// trace_body's kAccum changes, one per (search, step, mesh) a lean frame can
+// run, at their twins' workgroup size and waves per SIMD.  Entry points of
+// their own in a namespace of their own, as the corner-record kernels are: the
+// frame kernels above stay the code they were, and their names and parameter
+// types stay what tools/kernel_hash.py looks for.
+namespace accum {
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCorner>
+__global__ __launch_bounds__(trace_threads(kLds, kMesh, 0))
+__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, 0), 8)))
+void trace_kernel(AccumParams a) {
+    static_assert(!kCorner || (kBvh && kLds && kMesh == 0), "corner records: sphere-only LDS kernels");
+    trace_body<kBvh, kLds, kStep, kMesh, false, false, kCorner, true>(a.p, a.image, a.tail);
+}
+}  // namespace accum
+
 // ------------------------------------------------------------ resolve kernel
 // Sums each pixel's samples in order (common.rs:333-341), gamma + `as u8`
 // (:344-356), one RGBA8 word per pixel.  The slab is planar and pixel-major,
@@ -2000,23 +2084,36 @@ __global__ __launch_bounds__(kResolveWaves * 64) void resolve_kernel(
 }  // namespace
 
 // ------------------------------------------------------------ the instances
-// Every trace_kernel / corner::trace_kernel instance is spelled here and
-// nowhere else: launches, occupancy queries and the LDS opt-in look it up by
-// its TraceVariant (render.h).
+// Every trace_kernel / corner::trace_kernel / accum::trace_kernel instance is
+// spelled here and nowhere else: launches, occupancy queries and the LDS opt-in
+// look it up by its TraceVariant (render.h).
 struct TraceInstance {
     const void *fn;    // nullptr: no such instance
     uint32_t threads;  // per workgroup (the kernel's __launch_bounds__)
-    bool corner;       // takes CornerParams
+    bool corner;       // takes CornerParams (kKindAccum: AccumParams, whatever the search)
 };
-constexpr int kTraceVariants = 4 * 2 * 4 * 3;  // search x step x mesh x kind
-constexpr int trace_index(TraceVariant v) { return ((v.search * 2 + v.step) * 4 + v.mesh) * 3 + v.kind; }
+constexpr int kTraceKinds = 4;
+constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds;  // search x step x mesh x kind
+constexpr int trace_index(TraceVariant v) {
+    return ((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind;
+}
 
 template <int kI>
 static TraceInstance trace_instance_at() {
-    constexpr int kSearch = kI / 24, kMesh = kI / 3 % 4, kKind = kI % 3;
-    constexpr bool kStep = kI / 12 % 2 != 0, kCount = kKind == kKindCounting, kSerial = kKind == kKindSerial;
-    constexpr uint32_t threads = trace_threads(kSearch >= kSearchLdsBox, kMesh, kKind);
+    constexpr int kSearch = kI / (8 * kTraceKinds), kMesh = kI / kTraceKinds % 4, kKind = kI % kTraceKinds;
+    constexpr bool kStep = kI / (4 * kTraceKinds) % 2 != 0, kCount = kKind == kKindCounting,
+                   kSerial = kKind == kKindSerial, kAccum = kKind == kKindAccum;
+    // (an accumulation pass runs at its lean twin's workgroup size)
+    constexpr uint32_t threads = trace_threads(kSearch >= kSearchLdsBox, kMesh, kAccum ? (int)kKindLean : kKind);
     if constexpr (kSerial && kMesh == 3) {  // the SERIAL passes keep the binary triangle walk
+        return {nullptr, 0, false};
+    } else if constexpr (kAccum && kSearch != kSearchLdsCorner) {
+        return {reinterpret_cast<const void *>(
+                    &accum::trace_kernel<kSearch != kSearchBrute, kSearch == kSearchLdsBox, kStep, kMesh, false>),
+                threads, true};
+    } else if constexpr (kAccum && kMesh == 0) {
+        return {reinterpret_cast<const void *>(&accum::trace_kernel<true, true, kStep, 0, true>), threads, true};
+    } else if constexpr (kAccum) {
         return {nullptr, 0, false};
     } else if constexpr (kSearch != kSearchLdsCorner) {
         return {reinterpret_cast<const void *>(
@@ -2059,6 +2156,17 @@ hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t strea
     if (k.fn == nullptr) return hipErrorInvalidValue;
     CornerParams cp{p, corner};  // (begins with the TraceParams: either kernel's argument block)
     void *args[] = {k.corner ? (void *)&cp : (void *)&cp.p};
+    return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
+}
+
+hipError_t launch_trace_accum(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
+                              const AccumTail &tail) {
+    const TraceVariant v = trace_variant(p, corner != nullptr, kKindAccum);
+    const TraceInstance &k = trace_instance(trace_index(v));
+    // (the passes resolve in-kernel: without a ring the samples would go to the slab)
+    if (k.fn == nullptr || p.ring == nullptr || tail.sums == nullptr) return hipErrorInvalidValue;
+    AccumParams ap{p, v.search == kSearchLdsCorner ? corner : nullptr, tail};
+    void *args[] = {(void *)&ap};
     return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
 }
 

@@ -453,10 +453,16 @@ static int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel 
 
 int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t height,
                  const RtRenderOptions &o, uint32_t *d_out, hipStream_t stream,
-                 RtRenderStats *stats, const SerialPass *sp, const uint32_t *d_replay, bool defer_stats) {
+                 RtRenderStats *stats, const SerialPass *sp, const uint32_t *d_replay, bool defer_stats,
+                 const AccumPass *ap) {
     if (stats) std::memset(stats, 0, sizeof(*stats));
     const uint32_t nranks = o.nranks ? o.nranks : 1;
     if (o.rank >= nranks) { set_error("rank >= nranks"); return -1; }
+    if (ap && (sp || nranks != 1 || o.rng_mode == RT_RNG_SERIAL || o.samples_per_pixel < 1 ||
+               o.samples_per_pixel > 4096 || (o.flags & RT_FLAG_KEEP_SAMPLES))) {
+        set_error("accumulation pass: one rank, COUNTER or REPLAY, 1 to 4096 samples, fused resolve");
+        return -1;
+    }
     if (o.rng_mode == RT_RNG_SERIAL && !sp && !d_replay)
         return render_frame_serial(w, cam, width, height, o, d_out, stream, stats);
     if (!sp && o.rng_mode != RT_RNG_COUNTER && o.rng_mode != RT_RNG_REPLAY && !d_replay) {
@@ -490,8 +496,9 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // kernel writes the RGBA8 pixels.  The slab path (every sample to HBM, then
     // resolve_kernel) serves RT_FLAG_KEEP_SAMPLES and spp above 4096 (a ring
     // slot holds at least one whole pixel).
+    // (accumulation passes always resolve in-kernel: the fold continues there)
     const bool fused = spp > 0 && spp <= 4096 && !(o.flags & RT_FLAG_KEEP_SAMPLES) &&
-                       env_u64("RT_AMD_FUSED", 1) != 0;
+                       (ap != nullptr || env_u64("RT_AMD_FUSED", 1) != 0);
     // jobs per launch: 2^31 (fused: C3 in one launch) or 2^30 (a 12 GB slab)
     const uint64_t slab_jobs = env_u64("RT_AMD_SLAB_JOBS", fused ? (1ull << 31) - 1 : 1ull << 30);
     size_t rows_per_slab = jobs_per_row ? (size_t)std::max<uint64_t>(1, slab_jobs / jobs_per_row) : T;
@@ -676,13 +683,16 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         }
         p.tbvh_r = tb.radius; p.tbvh_mag = std::max(tb.mag, w.tcells.mag);
     }
-    const float inv_spp = 1.0f / (float)o.samples_per_pixel;  // 1.0 / spp as f32 (common.rs:345)
+    // (an accumulation pass writes the frame of all N = n0 + n samples held after it)
+    const uint32_t nheld = ap ? ap->n0 + spp : spp;
+    const float inv_spp = ap ? 1.0f / (float)nheld
+                             : 1.0f / (float)o.samples_per_pixel;  // 1.0 / spp as f32 (common.rs:345)
     p.inv_spp = inv_spp;
     {
         // every sample's alpha is exactly 1.0, so each pixel's
         // alpha byte is this one fold, done once (resolve_kernel does it per pixel)
         float a = 1.0f;  // Color::new(0,0,0) has alpha 1 (color.rs:21-23)
-        for (uint32_t k = 0; k < spp && a + 1.0f != a; ++k) a = a + 1.0f;
+        for (uint32_t k = 0; k < nheld && a + 1.0f != a; ++k) a = a + 1.0f;
         const float x = a * inv_spp * 255.999f;
         p.alpha_u8 = !(x > 0.0f) ? 0u : x >= 255.0f ? 255u : (uint32_t)x;  // saturating `as u8`
     }
@@ -706,15 +716,25 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     p.tri_walk_min = (uint32_t)env_u64("RT_AMD_TRI_WALK_MIN", wide_frame ? 64 : 32);
     const bool timed = stats != nullptr;  // HIP-event timing + counters need a host wait
     // launch_trace runs the counting kind iff p.stats (set below), the SERIAL instances for sp
-    const int ctv = sp ? kKindSerial : timed ? kKindCounting : kKindLean;
+    // (an accumulation pass: its own kind, which has no counting twin -- a timed
+    // pass gets its HIP-event times and schedule, the work counters stay 0)
+    const int ctv = sp ? kKindSerial : ap ? kKindAccum : timed ? kKindCounting : kKindLean;
     const TraceVariant tv = trace_variant(p, corner_img != nullptr, ctv);
+    if (ap && d->occupancy(tv) == 0) {
+        int blocks = 0;
+        HIP_TRY(trace_occupancy(&blocks, tv, trace_dyn_lds(p, tv)));
+        if (const uint64_t bpc = env_u64("RT_AMD_BLOCKS_PER_CU", 0))
+            if (tv.search != kSearchLdsCorner) blocks = (int)bpc;
+        if (blocks < 1 && tv.lds()) { set_error("accumulation kernel does not fit its LDS tree"); return -1; }
+        d->occupancy(tv) = std::max(blocks, 1);
+    }
     const uint64_t waves_per_block = trace_block_threads(tv) / 64;
     const uint64_t full_blocks = (uint64_t)d->occupancy(tv) * (uint64_t)d->num_cus;
     uint32_t launches = 0, waves = 0;
     // counters only when asked for: one 16-slot record per wave, summed here
-    const uint64_t max_waves = full_blocks * waves_per_block;
+    const uint64_t max_waves = ap ? 0 : full_blocks * waves_per_block;
     p.stats = nullptr;
-    if (timed) {
+    if (timed && !ap) {
         HIP_TRY(grow(d->stats, d->stats_cap, max_waves * kStatSlots));
         HIP_TRY(hipMemsetAsync(d->stats, 0, max_waves * kStatSlots * 8, s));
         p.stats = d->stats;
@@ -841,6 +861,16 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         return LaunchPlan{blocks, nwaves, chunk, parts, wpb * 64};
     };
     LaunchPlan lean_plan{0, 0, 0, 0, 0};  // the uncounted (timed) kernel's schedule of the last launch
+    AccumTail tail{};
+    if (ap) {
+        AccumState &acc = *ap->acc;
+        // the sums are the accumulator's own, not the device's scratch: a pass on
+        // another stream than the last one waits for it here
+        if (acc.done_stream && acc.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, acc.done, 0));
+        // the first pass (after creation or a reset) starts every fold from 0.0f
+        if (ap->n0 == 0) HIP_TRY(hipMemsetAsync(acc.sums, 0, 3 * width * height * sizeof(float), s));
+        tail = AccumTail{acc.sums, ap->n0, acc.stride};
+    }
     uint32_t nslab = 0;  // (counted frames: event triple per launch)
     for (size_t r0 = 0; r0 < T; r0 += rows_per_slab, ++nslab) {
         const size_t rows = std::min(rows_per_slab, T - r0);
@@ -858,6 +888,8 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         p.gj32 = nranks == 1 && (uint64_t)width * height * spp < (1ull << 32) ? 1u : 0u;
         p.gj_c0 = (uint32_t)(((uint64_t)height - 1 - r0) * width * spp);
         p.gj_2p = (uint32_t)(2ull * width * spp);
+        // (accumulation: jobs at the accumulator's stride, render.h AccumTail)
+        if (ap) p.gj32 = (uint64_t)width * height * ap->acc->stride < (1ull << 32) ? 1u : 0u;
         p.njobs = (uint32_t)njobs;
         p.npix = (uint32_t)(rows * width);
         if (timed) HIP_TRY(hipEventRecord(ev3[0], s));
@@ -881,13 +913,14 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
             if (!d->cset_clean[d->cset]) HIP_TRY(hipMemsetAsync(cur, 0, parts * 128, s));
             p.job_counter = cur;
             p.job_counter_next = d->counter + (size_t)(d->cset ^ 1u) * kMaxParts * 32;
-            HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img));
+            if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, corner_img, tail));
+            else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img));
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
             d->cset_clean[d->cset] = true;
             p.job_counter = d->counter;
             p.job_counter_next = nullptr;
-            lean_plan = ctv == 0 ? lp : plan(0, njobs);
+            lean_plan = ctv == kKindLean || ap ? lp : plan(kKindLean, njobs);
             d->last_jobs = fused ? 0 : njobs;
             d->last_spp = spp;
             d->last_fused = fused;  // rt_read_samples needs the slab
@@ -902,6 +935,10 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     }
     HIP_TRY(hipEventRecord(d->done, s));
     d->done_stream = s;
+    if (ap) {
+        HIP_TRY(hipEventRecord(ap->acc->done, s));
+        ap->acc->done_stream = s;
+    }
     // without stats the frame stays asynchronous on the stream (no host wait)
     if (!timed) return 0;
     // the wave records into pinned host memory (an asynchronous copy, so a
@@ -914,7 +951,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         HIP_TRY(hipHostMalloc((void **)&d->hrec, nrec * 8));
         d->hrec_cap = nrec;
     }
-    HIP_TRY(hipMemcpyAsync(d->hrec, d->stats, nrec * 8, hipMemcpyDeviceToHost, s));
+    if (nrec) HIP_TRY(hipMemcpyAsync(d->hrec, d->stats, nrec * 8, hipMemcpyDeviceToHost, s));
     auto &pd = d->pend;
     pd.active = true;
     pd.nrec = nrec;
@@ -1884,6 +1921,218 @@ int render_frame_host(WorldState &w, const CameraModel &cam, size_t width, size_
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(host_out, d->out, T * width * 4, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------ accumulation
+// (rt_accum_*: DESIGN.md 5.6)
+namespace {
+// guards AccumState::world and WorldState::accums (a world freed before its
+// accumulators detaches them)
+std::mutex g_accum_mu;
+
+void camera_floats(const CameraModel &cam, float out[12]) {
+    const Vec3 cv[4] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical};
+    for (int i = 0; i < 4; ++i) { out[3 * i] = cv[i].x; out[3 * i + 1] = cv[i].y; out[3 * i + 2] = cv[i].z; }
+}
+
+WorldState *accum_world(AccumState &a) {
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    if (!a.world) set_error("accumulator: its world was freed");
+    return a.world;
+}
+
+// The held samples count only for the camera and scene they were traced with
+// (the 12 camera floats compared as bits: a camera moved away and back matches)
+void accum_check_state(AccumState &a, WorldState &w, const float cam[12]) {
+    if (a.held != 0 && (std::memcmp(a.cam, cam, sizeof(a.cam)) != 0 || a.edit_version != w.edit_version)) a.held = 0;
+}
+
+void accum_release(AccumState *a) {
+    if (a->device >= 0 && hipSetDevice(a->device) == hipSuccess) {
+        if (a->done_stream) (void)hipEventSynchronize(a->done);
+        if (a->sums) (void)hipFree(a->sums);
+        if (a->replay) (void)hipFree(a->replay);
+        if (a->done) (void)hipEventDestroy(a->done);
+    }
+    delete a;
+}
+}  // namespace
+
+WorldState::~WorldState() {
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    for (AccumState *a : accums) a->world = nullptr;
+}
+
+AccumState *accum_create(WorldState &w, size_t width, size_t height, uint32_t stride, int32_t depth,
+                         uint32_t mode, uint32_t seed, const uint32_t *replay_states, int32_t device,
+                         int32_t accel) {
+    if (width == 0 || height == 0 || width > 0xFFFFFFu || height > 0xFFFFFFu ||
+        (uint64_t)width * height > 0xFFFFFFFFull) {
+        set_error("rt_accum_create: frame size must be 1 x 1 to 2^24 - 1 squared, below 2^32 pixels");
+        return nullptr;
+    }
+    if (stride == 0) { set_error("rt_accum_create: sample_stride must be at least 1"); return nullptr; }
+    if (mode == RT_RNG_SERIAL) {
+        set_error("rt_accum_create: RT_RNG_SERIAL cannot be accumulated (one stream over the whole frame "
+                  "has no per-pass meaning); use RT_RNG_COUNTER or RT_RNG_REPLAY");
+        return nullptr;
+    }
+    if (mode != RT_RNG_COUNTER && mode != RT_RNG_REPLAY) {
+        set_error("rt_accum_create: rng_mode must be RT_RNG_COUNTER or RT_RNG_REPLAY");
+        return nullptr;
+    }
+    if (mode == RT_RNG_REPLAY && !replay_states) {
+        set_error("rt_accum_create: replay table missing");
+        return nullptr;
+    }
+    std::lock_guard<std::recursive_mutex> lock(w.mu);
+    DeviceState *d = nullptr;
+    if (device_for(w, device, d)) return nullptr;
+    AccumState *a = new AccumState();
+    a->width = width; a->height = height; a->stride = stride;
+    a->depth = depth; a->device = d->device; a->accel = accel;
+    a->mode = mode; a->seed = seed;
+    auto fail = [&](hipError_t e, const char *what) -> AccumState * {
+        set_error(std::string("rt_accum_create: ") + what + " failed: " + hipGetErrorString(e));
+        accum_release(a);
+        return nullptr;
+    };
+    hipError_t e = hipEventCreateWithFlags(&a->done, hipEventDisableTiming);
+    if (e != hipSuccess) return fail(e, "hipEventCreate");
+    e = hipMalloc((void **)&a->sums, 3 * width * height * sizeof(float));
+    if (e != hipSuccess) return fail(e, "hipMalloc (sums)");
+    if (mode == RT_RNG_REPLAY) {
+        const size_t n = width * height * (size_t)stride;
+        e = hipMalloc((void **)&a->replay, n * 4);
+        if (e != hipSuccess) return fail(e, "hipMalloc (replay table)");
+        e = hipMemcpy(a->replay, replay_states, n * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(e, "hipMemcpy (replay table)");
+    }
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    a->world = &w;
+    w.accums.push_back(a);
+    return a;
+}
+
+void accum_free(AccumState *a) {
+    if (!a) return;
+    {
+        std::lock_guard<std::mutex> g(g_accum_mu);
+        if (a->world) {
+            auto &v = a->world->accums;
+            v.erase(std::remove(v.begin(), v.end(), a), v.end());
+            a->world = nullptr;
+        }
+    }
+    accum_release(a);
+}
+
+int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t *d_out, hipStream_t stream,
+              void *host_out, RtRenderStats *stats) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    WorldState &w = *wp;
+    std::lock_guard<std::recursive_mutex> lock(w.mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, w, cf);
+    if (nsamples <= 0) { set_error("rt_accum_add: nsamples must be at least 1"); return -1; }
+    if ((uint64_t)nsamples > (uint64_t)(a.stride - a.held)) {
+        set_error("rt_accum_add: " + std::to_string(a.held) + " + " + std::to_string(nsamples) +
+                  " samples exceed the accumulator's sample_stride " + std::to_string(a.stride));
+        return -1;
+    }
+    DeviceState *d = nullptr;
+    int rc = device_for(w, a.device, d);
+    if (rc) return rc;
+    hipStream_t s = stream ? stream : d->stream;
+    const size_t npix = a.width * a.height;
+    if (!d_out) {  // (the kernels always write the frame)
+        HIP_TRY(grow(d->out, d->out_cap, npix));
+        d_out = d->out;
+    }
+    RtRenderOptions o;
+    std::memset(&o, 0, sizeof(o));
+    o.max_ray_bounces = a.depth;
+    o.rng_mode = a.mode;
+    o.seed = a.seed;
+    o.nranks = 1;
+    o.device = a.device;
+    o.accel = a.accel;
+    std::memcpy(a.cam, cf, sizeof(cf));
+    a.edit_version = w.edit_version;
+    // a ring slot holds whole pixels of at most 4096 samples: larger requests
+    // run as consecutive passes (the same fold, continued)
+    uint32_t left = (uint32_t)nsamples;
+    RtRenderStats total{};
+    while (left) {
+        const uint32_t n = std::min<uint32_t>(left, 4096u);
+        o.samples_per_pixel = (int32_t)n;
+        const AccumPass ap{&a, a.held};
+        RtRenderStats st{};
+        rc = render_frame(w, cam, a.width, a.height, o, d_out, s, stats ? &st : nullptr, nullptr, a.replay, false,
+                          &ap);
+        if (rc) return rc;
+        a.held += n;
+        left -= n;
+        if (stats) {
+            const uint64_t samples = total.samples + st.samples;
+            const double ms = total.trace_ms + st.trace_ms, rms = total.resolve_ms + st.resolve_ms;
+            const uint32_t launches = total.trace_launches + st.trace_launches;
+            total = st;  // (schedule and path: the last pass's)
+            total.samples = samples;
+            total.trace_ms = ms;
+            total.resolve_ms = rms;
+            total.trace_launches = launches;
+        }
+    }
+    if (stats) *stats = total;
+    if (host_out) {
+        HIP_TRY(hipMemcpyAsync(host_out, d_out, npix * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+long accum_samples(AccumState &a, const CameraModel &cam) {
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    std::lock_guard<std::recursive_mutex> lock(wp->mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, *wp, cf);
+    return (long)a.held;
+}
+
+int accum_read(AccumState &a, const CameraModel &cam, float *sums) {
+    if (!sums) { set_error("rt_accum_read: null output"); return -1; }
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    std::lock_guard<std::recursive_mutex> lock(wp->mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, *wp, cf);
+    const size_t npix = a.width * a.height;
+    if (a.held == 0) {  // (a reset only sets N: the next pass zero-fills the planes)
+        std::fill(sums, sums + 3 * npix, 0.0f);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(a.device));
+    HIP_TRY(hipEventSynchronize(a.done));
+    std::vector<float> planes(3 * npix);
+    HIP_TRY(hipMemcpy(planes.data(), a.sums, 3 * npix * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i)
+        for (size_t c = 0; c < 3; ++c) sums[3 * i + c] = planes[c * npix + i];
+    return 0;
+}
+
+int accum_reset(AccumState &a) {
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    std::lock_guard<std::recursive_mutex> lock(wp->mu);
+    a.held = 0;
     return 0;
 }
 

@@ -111,7 +111,13 @@ struct DeviceState {
     // TraceVariant), [search][kind][step], queried once at device setup for the
     // scene's family (the corner search: frame kinds only)
     int blocks_per_cu[4][3][2] = {};
-    int &occupancy(TraceVariant v) { return blocks_per_cu[v.search][v.kind][v.step]; }
+    // (the accumulation kind: queried by the first pass that runs an instance,
+    // 0 until then; same workgroup size, LDS request and waves per SIMD as the
+    // lean twin the set-up's decisions were made with)
+    int accum_blocks_per_cu[4][2] = {};
+    int &occupancy(TraceVariant v) {
+        return v.kind == kKindAccum ? accum_blocks_per_cu[v.search][v.step] : blocks_per_cu[v.search][v.kind][v.step];
+    }
     int num_cus = 0;
     // a counted frame's timing events (3 per launch: start, trace end, resolve
     // end) and its wave records copied to pinned host memory; with
@@ -134,6 +140,8 @@ struct DeviceState {
     bool last_fused = false;                                    // it resolved in-kernel (no slab)
     ~DeviceState();
 };
+
+struct AccumState;
 
 struct WorldState {
     SceneModel scene;
@@ -159,9 +167,42 @@ struct WorldState {
     struct SplJob { std::future<PrimarySphereLists> f; CameraModel cam{}; size_t w = 0, h = 0; };
     SplJob spl_job;
     std::map<int, std::unique_ptr<DeviceState>> devices;
+    // bumped by every scene edit (rt_world_set_*_material): an accumulator
+    // whose samples were traced under another value starts over
+    uint64_t edit_version = 0;
+    // the accumulators created on this world (accum_create / accum_free);
+    // the world's destructor detaches them, after which their calls fail
+    std::vector<AccumState *> accums;
     // one frame at a time per handle: calls from several host threads are
     // serialised here (render_frame_multi re-enters render_frame)
     std::recursive_mutex mu;
+    ~WorldState();
+};
+
+// A progressive accumulation: per-pixel f32 sums of sample
+// colours for one world, frame size and camera, on one device, filled in
+// passes.  Owns the sum planes and, in REPLAY mode, the device copy of its
+// start-state table; the device's scratch stays shared with the frames.
+struct AccumState {
+    WorldState *world = nullptr;  // nullptr: the world was freed first
+    size_t width = 0, height = 0;
+    uint32_t stride = 0;          // S: samples per pixel at most, the job stride
+    int32_t depth = 0, device = -1, accel = 0;
+    uint32_t mode = 0, seed = 0;
+    uint32_t held = 0;            // N: samples per pixel in the sums
+    float cam[12] = {};           // the camera they were traced with ...
+    uint64_t edit_version = 0;    // ... and the scene version
+    float *sums = nullptr;        // 3 planes of width * height (R, G, B), top row first
+    uint32_t *replay = nullptr;   // REPLAY: width * height * stride start states
+    hipEvent_t done = nullptr;    // end of the last pass ...
+    hipStream_t done_stream = nullptr;  // ... and the stream it ran on (nullptr: none yet)
+};
+
+// One pass of an accumulation, for render_frame: n0 samples held, the frame's
+// o.samples_per_pixel more are traced (1..4096).
+struct AccumPass {
+    AccumState *acc;
+    uint32_t n0;
 };
 
 // One launch of a SERIAL-mode pass (render_frame_serial): the frame's jobs are
@@ -197,7 +238,27 @@ struct SerialPass {
 int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t height,
                  const RtRenderOptions &opts, uint32_t *d_out, hipStream_t stream,
                  RtRenderStats *stats, const SerialPass *sp = nullptr,
-                 const uint32_t *d_replay = nullptr, bool defer_stats = false);
+                 const uint32_t *d_replay = nullptr, bool defer_stats = false,
+                 const AccumPass *ap = nullptr);
+// (ap: the frame is that accumulation pass -- o.samples_per_pixel more samples
+// per pixel folded into ap->acc's sums, d_out the frame of all samples held)
+
+// Progressive accumulation (rt_accum_*, include/raytracer_amd.h).  create
+// allocates on o.device (or the current device), uploads the REPLAY table and
+// registers the accumulator with the world.  add: n more samples per pixel
+// (passes of <= 4096), the frame of all held samples to d_out (device, or
+// nullptr) and host_out (or nullptr); with host_out or stats it waits for the
+// pass.  Camera moves and scene edits since the held samples were traced
+// reset it first (accum_samples and accum_read see the same rule).
+AccumState *accum_create(WorldState &w, size_t width, size_t height, uint32_t stride, int32_t depth,
+                         uint32_t mode, uint32_t seed, const uint32_t *replay_states, int32_t device,
+                         int32_t accel);
+int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t *d_out, hipStream_t stream,
+              void *host_out, RtRenderStats *stats);
+long accum_samples(AccumState &a, const CameraModel &cam);
+int accum_read(AccumState &a, const CameraModel &cam, float *sums);
+int accum_reset(AccumState &a);
+void accum_free(AccumState *a);
 // Waits for device d's pending counted frame and fills stats from it.
 int collect_frame_stats(DeviceState *d, RtRenderStats *stats);
 

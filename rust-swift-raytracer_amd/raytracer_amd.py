@@ -32,6 +32,8 @@ EXPORTS = (
     "rt_world_num_triangles", "rt_world_sphere", "rt_world_triangle", "rt_camera_get",
     "rt_last_parse_error", "rt_write_ppm", "rt_device_count", "rt_comm_count",
     "rt_world_set_sphere_material", "rt_world_set_triangle_material", "rt_assemble_tiles",
+    "rt_accum_default_options", "rt_accum_create", "rt_accum_add", "rt_accum_add_device",
+    "rt_accum_samples", "rt_accum_read", "rt_accum_reset", "rt_accum_free",
 )
 
 
@@ -57,6 +59,12 @@ class RenderOptions(C.Structure):
                 ("replay_states", C.POINTER(C.c_uint32)), ("row_block", C.c_uint32),
                 ("rank", C.c_uint32), ("nranks", C.c_uint32), ("device", C.c_int32),
                 ("accel", C.c_int32), ("flags", C.c_uint32), ("ndevices", C.c_int32)]
+
+
+class AccumOptions(C.Structure):
+    _fields_ = [("max_ray_bounces", C.c_int32), ("rng_mode", C.c_uint32), ("seed", C.c_uint32),
+                ("replay_states", C.POINTER(C.c_uint32)), ("sample_stride", C.c_uint32),
+                ("device", C.c_int32), ("accel", C.c_int32)]
 
 
 class RenderStats(C.Structure):
@@ -154,6 +162,22 @@ def lib(path=None):
         L.rt_assemble_tiles.restype = C.c_int
         L.rt_assemble_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                         C.c_uint32, C.c_size_t, C.c_void_p]
+        if hasattr(L, "rt_accum_create"):  # (an older build loaded for an A/B run has none)
+            L.rt_accum_default_options.argtypes = [C.POINTER(AccumOptions)]
+            L.rt_accum_create.restype = C.c_void_p
+            L.rt_accum_create.argtypes = [H, C.c_size_t, C.c_size_t, C.POINTER(AccumOptions)]
+            L.rt_accum_add.restype = C.c_int
+            L.rt_accum_add.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ColorU8), C.POINTER(RenderStats)]
+            L.rt_accum_add_device.restype = C.c_int
+            L.rt_accum_add_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.POINTER(RenderStats)]
+            L.rt_accum_samples.restype = C.c_long
+            L.rt_accum_samples.argtypes = [C.c_void_p]
+            L.rt_accum_read.restype = C.c_int
+            L.rt_accum_read.argtypes = [C.c_void_p, fp]
+            L.rt_accum_reset.restype = C.c_int
+            L.rt_accum_reset.argtypes = [C.c_void_p]
+            L.rt_accum_free.argtypes = [C.c_void_p]
         _libs[path] = L
     return _libs[path]
 
@@ -307,6 +331,12 @@ class World:
             raise RenderError(f"rt_render_ex failed ({rc}): {self._L.rt_last_error().decode()}")
         return px, (st.as_dict() if stats else None)
 
+    def accumulator(self, width, height, stride, depth=8, mode=RNG_COUNTER, seed=DEFAULT_SEED,
+                    replay=None, accel=ACCEL_AUTO, device=-1):
+        """rt_accum_create: a progressive accumulation of this world's frame at
+        its current camera, `stride` samples per pixel at most (Accumulator)."""
+        return Accumulator(self, width, height, stride, depth, mode, seed, replay, accel, device)
+
     def read_samples(self, njobs, device=-1):
         """Per-sample colours of the last trace launch: float32[njobs, 4]."""
         out = np.zeros((njobs, 4), np.float32)
@@ -331,6 +361,76 @@ class World:
         if rc != 0:
             raise RenderError(f"rt_render_device failed ({rc}): {self._L.rt_last_error().decode()}")
         return st.as_dict() if stats else None
+
+
+class Accumulator:
+    """rt_accum_*: a progressive accumulation of one world's frame (World.accumulator).
+    Holds its World, so the world outlives it."""
+
+    def __init__(self, world, width, height, stride, depth=8, mode=RNG_COUNTER, seed=DEFAULT_SEED,
+                 replay=None, accel=ACCEL_AUTO, device=-1):
+        self._world, self._L = world, world._L
+        self.width, self.height, self.stride = width, height, stride
+        o = AccumOptions()
+        self._L.rt_accum_default_options(C.byref(o))
+        o.max_ray_bounces, o.rng_mode, o.seed, o.sample_stride = depth, mode, seed, stride
+        o.device, o.accel = device, accel
+        keep = None
+        if replay is not None:
+            keep = np.ascontiguousarray(replay, dtype=np.uint32)
+            if keep.size != width * height * stride:
+                raise ValueError("replay table must hold width * height * stride states")
+            o.replay_states = keep.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._a = self._L.rt_accum_create(world.handle, width, height, C.byref(o))
+        del keep  # (uploaded at creation)
+        if not self._a:
+            raise RenderError(f"rt_accum_create failed: {self._L.rt_last_error().decode()}")
+
+    def close(self):
+        if getattr(self, "_a", None):
+            self._L.rt_accum_free(self._a)
+            self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise RenderError(f"{what} failed ({rc}): {self._L.rt_last_error().decode()}")
+        return rc
+
+    def add(self, n, stats=True):
+        """n more samples per pixel -> (rgba uint8[height, width, 4] of all held samples, stats dict)."""
+        px = np.zeros((self.height, self.width, 4), np.uint8)
+        st = RenderStats()
+        self._check(self._L.rt_accum_add(self._a, n, px.ctypes.data_as(C.POINTER(ColorU8)),
+                                         C.byref(st) if stats else None), "rt_accum_add")
+        return px, (st.as_dict() if stats else None)
+
+    def add_device(self, n, out_ptr, stream_ptr=0, stats=False):
+        """rt_accum_add_device: the frame into device memory (out_ptr 0: accumulate only);
+        without stats the pass is only enqueued on the stream."""
+        st = RenderStats()
+        self._check(self._L.rt_accum_add_device(self._a, n, C.c_void_p(out_ptr or None),
+                                                C.c_void_p(stream_ptr or None),
+                                                C.byref(st) if stats else None), "rt_accum_add_device")
+        return st.as_dict() if stats else None
+
+    @property
+    def samples(self):
+        return int(self._check(self._L.rt_accum_samples(self._a), "rt_accum_samples"))
+
+    def sums(self):
+        """The raw f32 sums: float32[height, width, 3], top row first."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        self._check(self._L.rt_accum_read(self._a, out.ctypes.data_as(C.POINTER(C.c_float))), "rt_accum_read")
+        return out
+
+    def reset(self):
+        self._check(self._L.rt_accum_reset(self._a), "rt_accum_reset")
 
 
 def write_ppm(rgba: np.ndarray, path: str):
