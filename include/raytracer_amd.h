@@ -240,7 +240,10 @@ RtAccum *rt_accum_create(const Rust_WorldHandle *handle, size_t width, size_t he
 int rt_accum_add(RtAccum *acc, int64_t nsamples, Rust_ColorU8 *pixels, RtRenderStats *stats);
 /* Same, the frame to DEVICE memory d_rgba (NULL: accumulate only) on
  * hip_stream (NULL = the library's stream).  With stats == NULL the pass is
- * only enqueued (no host wait), like rt_render_device. */
+ * only enqueued (no host wait), like rt_render_device -- except on an adaptive
+ * accumulator (rt_adapt_enable below), whose deciding passes read the new list
+ * length back and wait on the host, as RT_RNG_SERIAL does in rt_render_device;
+ * do not call those inside a stream capture. */
 int rt_accum_add_device(RtAccum *acc, int64_t nsamples, void *d_rgba, void *hip_stream,
                         RtRenderStats *stats);
 /* Samples per pixel held (0 after a reset, also one that the next add would
@@ -252,6 +255,68 @@ int rt_accum_read(RtAccum *acc, float *sums);
 /* Forgets the held samples (the next pass starts from zero sums). */
 int rt_accum_reset(RtAccum *acc);
 void rt_accum_free(RtAccum *acc);
+
+/* Adaptive accumulation: stop sampling pixels that have converged (DESIGN.md
+ * 5.7).
+ *
+ * An accumulator that holds no samples can be switched to adaptive.  Besides
+ * its three sums it then owns, per pixel, sumsq (f32: the in-order fold
+ * q <- q + y*y over the pixel's samples, y = (r + g) + b of the sample's
+ * colour, every operation one rounded f32 operation, the product rounded
+ * before the add) and count (u32: samples the pixel holds); the RGBA8 frame (a
+ * pixel that stopped keeps the bytes of its last pass); and the active list,
+ * the frame indices (top row first, ascending) of the pixels still sampled.
+ * All active pixels hold the same N, which rt_accum_samples returns.
+ *
+ * With N0 samples held by the active pixels, rt_accum_add(n) traces samples
+ * N0 .. N0+n-1 of the listed pixels only (same jobs g as above), continues
+ * their four folds and writes their RGBA8 at N = N0 + n.  If N >= min_samples
+ * it then decides per listed pixel, in f32, one rounded operation each:
+ *   inv = 1.0f / (float)N
+ *   m   = ((R + G) + B) * inv
+ *   v   = q * inv - m * m;  v = v < 0 ? 0 : v        (NaN stays NaN)
+ *   e   = v * inv
+ *   lim = tolerance * (m + bias)
+ *   converged iff e <= lim * lim                      (false for NaN)
+ * Converged pixels leave the list (order kept) and never return until a reset;
+ * count becomes N for every pixel the pass traced.  So each pixel always
+ * carries exactly the in-order fold of its own first count samples.
+ *
+ * Camera moves, scene edits and rt_accum_reset make every pixel active again
+ * with zero counts; the adaptive setting stays.  A pass with an empty list
+ * traces nothing, leaves N alone, still delivers the frame and returns 0; a
+ * pass beyond S stays an error.  Requests above 4096 samples run as
+ * consecutive passes, each with its decision.  A viewer's loop becomes "move,
+ * add while rt_adapt_active > 0, show".
+ *
+ * A deciding pass reads the new list length back (4 bytes) and therefore
+ * waits on the host for the pass, also with stats == NULL in
+ * rt_accum_add_device -- like RT_RNG_SERIAL in rt_render_device; do not call
+ * it inside a stream capture. */
+typedef struct RtAdaptOptions {
+  float tolerance;       /* relative standard error of the mean to stop at      */
+  float bias;            /* added to the mean: dark pixels stop on an absolute  */
+  uint32_t min_samples;  /* no decision before a pixel holds this many (>= 2)   */
+} RtAdaptOptions;
+
+/* tolerance 0.05, bias 0.05, min_samples 8. */
+void rt_adapt_default_options(RtAdaptOptions *opts);
+/* Switches to adaptive (opts NULL = the defaults).  An error unless the
+ * accumulator holds 0 samples; tolerance and bias must be finite and >= 0,
+ * min_samples >= 2.  0 or a negative error. */
+int rt_adapt_enable(RtAccum *acc, const RtAdaptOptions *opts);
+/* Back to every pixel every pass; an error unless 0 samples are held. */
+int rt_adapt_disable(RtAccum *acc);
+/* Pixels on the active list (width*height with no samples held or when the
+ * accumulator is not adaptive), or a negative error. */
+long rt_adapt_active(RtAccum *acc);
+/* count and sumsq: width*height values, top row first (all 0 with no samples
+ * held).  Adaptive accumulators only.  Wait for the last pass. */
+int rt_adapt_read_counts(RtAccum *acc, uint32_t *counts);
+int rt_adapt_read_sumsq(RtAccum *acc, float *sumsq);
+/* Copies at most cap entries of the active list and returns its length (list
+ * may be NULL with cap 0), or a negative error. */
+long rt_adapt_read_active(RtAccum *acc, uint32_t *list, size_t cap);
 
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).

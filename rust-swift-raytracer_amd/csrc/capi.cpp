@@ -384,6 +384,57 @@ void rt_accum_free(RtAccum *acc) {
     delete acc;
 }
 
+// ---- adaptive accumulation
+void rt_adapt_default_options(RtAdaptOptions *o) {
+    o->tolerance = 0.05f;
+    o->bias = 0.05f;
+    o->min_samples = 8;
+}
+
+int rt_adapt_enable(RtAccum *acc, const RtAdaptOptions *opts) {
+    RtAdaptOptions o;
+    if (opts) o = *opts;
+    else rt_adapt_default_options(&o);
+    // (the options first: a caller's mistake shows whatever the accumulator's state)
+    if (!(o.tolerance >= 0.0f) || !(o.tolerance <= 3.4028234663852886e38f) || !(o.bias >= 0.0f) ||
+        !(o.bias <= 3.4028234663852886e38f)) {
+        rtamd::set_error("rt_adapt_enable: tolerance and bias must be finite and >= 0");
+        return -1;
+    }
+    if (o.min_samples < 2) {
+        rtamd::set_error("rt_adapt_enable: min_samples must be at least 2");
+        return -1;
+    }
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_enable");
+    if (!cam) return -1;
+    return rtamd::adapt_enable(*acc->state, *cam, o.tolerance, o.bias, o.min_samples);
+}
+
+int rt_adapt_disable(RtAccum *acc) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_disable");
+    return cam ? rtamd::adapt_disable(*acc->state, *cam) : -1;
+}
+
+long rt_adapt_active(RtAccum *acc) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_active");
+    return cam ? rtamd::adapt_active(*acc->state, *cam) : -1;
+}
+
+int rt_adapt_read_counts(RtAccum *acc, uint32_t *counts) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_read_counts");
+    return cam ? rtamd::adapt_read_counts(*acc->state, *cam, counts) : -1;
+}
+
+int rt_adapt_read_sumsq(RtAccum *acc, float *sumsq) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_read_sumsq");
+    return cam ? rtamd::adapt_read_sumsq(*acc->state, *cam, sumsq) : -1;
+}
+
+long rt_adapt_read_active(RtAccum *acc, uint32_t *list, size_t cap) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_read_active");
+    return cam ? rtamd::adapt_read_active(*acc->state, *cam, list, cap) : -1;
+}
+
 int rt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

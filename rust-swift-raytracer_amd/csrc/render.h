@@ -215,9 +215,11 @@ inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : 
 //   mesh:   trace_mesh_kind, or 3: triangle trees walked through the 4-wide
 //           image (TraceParams::tw_nodes)
 //   kind:   what the jobs are (kKindAccum: one pass of a progressive
-//           accumulation, launch_trace_accum; lean-like, no counters)
+//           accumulation, launch_trace_accum; lean-like, no counters;
+//           kKindAdapt: its adaptive twin, launch_trace_adapt, whose pixels come
+//           from a list)
 enum : int { kSearchBrute = 0, kSearchGlobal = 1, kSearchLdsBox = 2, kSearchLdsCorner = 3 };
-enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2, kKindAccum = 3 };
+enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2, kKindAccum = 3, kKindAdapt = 4 };
 struct TraceVariant {
     int search;
     bool step;
@@ -266,6 +268,38 @@ struct AccumTail {
 };
 hipError_t launch_trace_accum(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
                               const AccumTail &tail);
+// One pass of an adaptive accumulation, instance
+// trace_variant(p, corner != nullptr, kKindAdapt): launch_trace_accum's pass
+// over the p.npix pixels of `list` only.  Launch-local pixel lp is frame pixel
+// list[lp] (index into p.out, top row first; p.slab_row0 = 0): its row, column,
+// global job and primary-list records derive from that, and the chunk resolve
+// maps through the list as well.  The resolve continues a fourth fold per
+// pixel, sumsq[pixel] <- sumsq + y y with y = (r + g) + b of each sample in
+// order (one rounded f32 operation each, no contraction).
+struct AdaptTail {
+    float *sums;
+    float *sumsq;
+    const uint32_t *list;
+    uint32_t n0, stride;
+};
+hipError_t launch_trace_adapt(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
+                              const AdaptTail &tail);
+// The adaptive accumulator's list kernels (adapt.hip).  iota: list[i] = i.
+// select: one thread per entry i < n of list: count[list[i]] = N and, with
+// decide, keep[i] = 0 iff the pixel converged by the rule of DESIGN.md 5.7
+// (keep[i] = 1 without decide); sums: three planes `plane` floats apart.
+// compact: out = the entries of list whose keep flag is set, in order (wave
+// ballot + mbcnt, an LDS scan per workgroup, one workgroup over the block
+// totals, the scatter: no atomic decides a position); *len = their number.
+// totals: scratch of adapt_compact_blocks(n) u32.
+hipError_t launch_adapt_iota(uint32_t *list, uint32_t n, hipStream_t stream);
+hipError_t launch_adapt_select(const uint32_t *list, uint32_t n, const float *sums, const float *sumsq,
+                               size_t plane, uint32_t *count, uint32_t *keep, uint32_t N, float inv,
+                               float tolerance, float bias, bool decide, hipStream_t stream);
+hipError_t launch_adapt_compact(const uint32_t *list, const uint32_t *keep, uint32_t n, uint32_t *totals,
+                                uint32_t *out, uint32_t *len, hipStream_t stream);
+constexpr uint32_t kAdaptBlock = 256;  // entries per workgroup of the list kernels
+inline size_t adapt_compact_blocks(size_t n) { return (n + kAdaptBlock - 1) / kAdaptBlock; }
 // Primary sphere lists built on the device (bvh.h build_primary_sphere_lists,
 // the same double arithmetic per sphere, then one thread per pixel collecting
 // the spheres whose projected box covers it, in tree order): rec gets 2 u32

@@ -837,6 +837,23 @@ __device__ __forceinline__ void tri_primary_list(const TraceParams &p, uint32_t 
         tri_record(p.cam_tris + 4u * p.ptl_items[j], org, dir, best_t, tri_t, tri_i, tri_in);
 }
 
+// The same for an adaptive accumulation pass (render.h AdaptTail): the job's
+// launch-local pixel is frame pixel list[lp] (top row first).
+__device__ __forceinline__ void tri_primary_list_adapt(const TraceParams &p, const uint32_t *list, uint32_t job,
+                                                       F3 org, F3 dir, float best_t, float &tri_t, int &tri_i,
+                                                       uint32_t &tri_in, uint32_t &tri_done) {
+    const uint32_t idx = list[fdiv(job, p.div_spp)];
+    const uint32_t q = fdiv(idx, p.div_width);
+    const uint32_t col = idx - q * p.width, row = p.height - 1u - q;
+    const uint32_t strip = row * p.ptl_spr + col / kPrimaryTriStripW;
+    const uint32_t b = p.ptl_off[strip], e = p.ptl_off[strip + 1];
+    tri_done += (e - b) + (p.ptl_end - p.ptl_always);
+    for (uint32_t j = b; j < e; ++j)
+        tri_record(p.cam_tris + 4u * p.ptl_items[j], org, dir, best_t, tri_t, tri_i, tri_in);
+    for (uint32_t j = p.ptl_always; j < p.ptl_end; ++j)
+        tri_record(p.cam_tris + 4u * p.ptl_items[j], org, dir, best_t, tri_t, tri_i, tri_in);
+}
+
 // One resolved pixel: gamma + `as u8` (common.rs:344-356), RGBA8 at the
 // tile row of launch-local pixel lp.
 __device__ __forceinline__ uint32_t resolve_channel(const TraceParams &p, float sum) {
@@ -952,6 +969,83 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
             held[2 * hplane] = b;
         }
         resolve_store(p, pix0 + i, r, g, b);
+    }
+}
+
+// The chunk resolve of an adaptive accumulation pass (render.h AdaptTail):
+// resolve_chunk<., kAccum> with every pixel index mapped through the pass's
+// list (launch-local pixel lp is frame pixel list[lp]) and a fourth fold per
+// pixel, q <- q + y y with y = (r + g) + b of each ring sample in sample order,
+// starting from the stored sumsq and stored back (each operation rounded on
+// its own: this file compiles without contraction).  Plane lanes: a fourth
+// lane group folds q, so the shape needs 4 * pixels <= 64; pixel lanes: a
+// fourth running value.  RGBA8 goes to p.out[list[lp]].
+template <bool kPlaneLanes>
+__device__ __forceinline__ void resolve_chunk_adapt(const TraceParams &p, const float *ring, uint32_t plane,
+                                                    uint32_t off, uint32_t base, uint32_t len, uint32_t lane,
+                                                    float *sums, float *sumsq, const uint32_t *list) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const uint32_t spp = p.spp;
+    const uint32_t np = fdiv(len, p.div_spp), pix0 = fdiv(base, p.div_spp);
+    const size_t hplane = (size_t)p.width * p.height;
+    if (kPlaneLanes && 4u * np <= kWave && (spp & 3u) == 0) {
+        const uint32_t c = lane >= np ? (lane >= 2u * np ? (lane >= 3u * np ? 3u : 2u) : 1u) : 0u;
+        const uint32_t g = lane - c * np;
+        const bool on = lane < 4u * np;
+        const size_t idx = list[pix0 + (on ? g : 0u)];
+        const float *src = ring + off + (on ? g : 0u) * spp;  // the pixel's R samples
+        float *held = (c < 3u ? sums + (size_t)c * hplane : sumsq) + idx;
+        float acc = on ? *held : 0.0f;
+        if (on) {
+            if (c < 3u) {
+                for (uint32_t k = 0; k < spp; k += 4u) {
+                    const float4 v = *reinterpret_cast<const float4 *>(src + c * plane + k);
+                    acc = acc + v.x;
+                    acc = acc + v.y;
+                    acc = acc + v.z;
+                    acc = acc + v.w;
+                }
+            } else {
+                for (uint32_t k = 0; k < spp; k += 4u) {
+                    const float4 r = *reinterpret_cast<const float4 *>(src + k);
+                    const float4 gg = *reinterpret_cast<const float4 *>(src + plane + k);
+                    const float4 b = *reinterpret_cast<const float4 *>(src + 2u * plane + k);
+                    const float y0 = (r.x + gg.x) + b.x, y1 = (r.y + gg.y) + b.y;
+                    const float y2 = (r.z + gg.z) + b.z, y3 = (r.w + gg.w) + b.w;
+                    acc = acc + y0 * y0;
+                    acc = acc + y1 * y1;
+                    acc = acc + y2 * y2;
+                    acc = acc + y3 * y3;
+                }
+            }
+            *held = acc;
+        }
+        const uint32_t ch = resolve_channel(p, acc);
+        const uint32_t G = (uint32_t)__shfl((int)ch, (int)(lane < np ? np + lane : lane));
+        const uint32_t B = (uint32_t)__shfl((int)ch, (int)(lane < np ? 2u * np + lane : lane));
+        if (lane < np) p.out[idx] = ch | (G << 8) | (B << 16) | (p.alpha_u8 << 24);
+        return;
+    }
+    for (uint32_t i = lane; i < np; i += kWave) {
+        const float *src = ring + off + i * spp;
+        const size_t idx = list[pix0 + i];
+        float *held = sums + idx;
+        float r = held[0], g = held[hplane], b = held[2 * hplane], q = sumsq[idx];
+        for (uint32_t k = 0; k < spp; ++k) {
+            const float sr = src[k], sg = src[plane + k], sb = src[2 * plane + k];
+            r = r + sr;
+            g = g + sg;
+            b = b + sb;
+            const float y = (sr + sg) + sb;
+            q = q + y * y;
+        }
+        held[0] = r;
+        held[hplane] = g;
+        held[2 * hplane] = b;
+        sumsq[idx] = q;
+        p.out[idx] = resolve_channel(p, r) | (resolve_channel(p, g) << 8) | (resolve_channel(p, b) << 16) |
+                     (p.alpha_u8 << 24);
     }
 }
 
@@ -1122,9 +1216,20 @@ struct AccumParams {
     const uint4 *image;
     AccumTail tail;
 };
+// kAdapt: one pass of an adaptive accumulation (adapt::trace_kernel below):
+// the pass's pixels are those of a list (render.h AdaptTail).  The refill maps
+// the job's launch-local pixel through it, and so does the chunk resolve
+// (resolve_chunk_adapt); nothing else changes.
+struct AdaptParams {
+    TraceParams p;
+    const uint4 *image;
+    AdaptTail tail;
+};
 template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner,
-          bool kAccum = false>
-__device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, AccumTail tail = AccumTail{}) {
+          bool kAccum = false, bool kAdapt = false>
+__device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, AccumTail tail = AccumTail{},
+                                           AdaptTail xtail_arg = AdaptTail{}) {
+    static_assert(!(kAccum && kAdapt), "an adaptive pass is an instance of its own");
     // SERIAL count passes: the walk of the previous pass set the first sample
     // and this iteration's candidates per sample (ctrl[5], <= the launch's K)
     if (kSerial && p.ctrl != nullptr) {
@@ -1189,6 +1294,17 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
         return ((const AccumParams *)kp)->tail;
 #else
         return tail;
+#endif
+    };
+    // (kAdapt) likewise
+    auto xtail = [&]() -> const AdaptTail & {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_NO_KARG_RELOAD)
+        const __attribute__((address_space(4))) AdaptParams *kp =
+            (const __attribute__((address_space(4))) AdaptParams *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));
+        return ((const AdaptParams *)kp)->tail;
+#else
+        return xtail_arg;
 #endif
     };
     extern __shared__ float4 lds[];
@@ -1455,7 +1571,10 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     if (tri_begin(p, org, dir, best_t, cam, e, tri_t, tri_i, tri_in, tri_done)) {
                         // (the lists index the camera-origin records, which exist
                         // without the camera tree's nodes: runtime.cpp prepare_camera)
-                        if (bounce == 0 && p.ptl_off != nullptr) {
+                        if (kAdapt && bounce == 0 && p.ptl_off != nullptr) {
+                            tri_primary_list_adapt(p, xtail().list, lane_job(slot), org, dir, best_t, tri_t, tri_i,
+                                                   tri_in, tri_done);
+                        } else if (bounce == 0 && p.ptl_off != nullptr) {
                             tri_primary_list<kSerial>(p, lane_job(slot), org, dir, best_t, tri_t, tri_i, tri_in,
                                              tri_done);
                         } else {
@@ -1752,7 +1871,12 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     rleft[k] -= n;
                     if (n != 0 && rleft[k] == 0) {
                         const TraceParams &pc = kargs();
-                        if (kAccum)
+                        if (kAdapt) {
+                            const AdaptTail &t = xtail();
+                            resolve_chunk_adapt<RT_PLANE_LANES(kMesh)>(pc, sbase, pstride, k << pc.ring_shift,
+                                                                       rbase[k], rlen[k], lane, t.sums, t.sumsq,
+                                                                       t.list);
+                        } else if (kAccum)
                             resolve_chunk<RT_PLANE_LANES(kMesh), true>(pc, sbase, pstride, k << pc.ring_shift,
                                                                        rbase[k], rlen[k], lane, atail().sums);
                         else if (!(pc.ablate & 2u))
@@ -1856,7 +1980,20 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                 // enumeration order changes no bits.
                 uint32_t s, col, row;
                 uint64_t gjob = 0;
-                if (kAccum) {
+                if (kAdapt) {
+                    // the pass's pixel lp is frame pixel list[lp] (top row first);
+                    // its job as in an accumulation pass
+                    const AdaptTail &t = xtail();
+                    const uint32_t lp = fdiv(job, pc.div_spp);
+                    const uint32_t idx = t.list[lp];
+                    const uint32_t q = fdiv(idx, pc.div_width);
+                    s = job - lp * pc.spp;
+                    col = idx - q * pc.width;
+                    row = pc.height - 1u - q;
+                    const uint32_t pix = row * pc.width + col;
+                    if (pc.gj32) gjob = pix * t.stride + (t.n0 + s);  // (W H S < 2^32)
+                    else gjob = (uint64_t)pix * t.stride + (t.n0 + s);
+                } else if (kAccum) {
                     // sample N0 + s of the pixel, its job at the accumulator's
                     // sample stride (whole frames of one rank: tile row = image row)
                     const AccumTail &t = atail();
@@ -2016,6 +2153,19 @@ void trace_kernel(AccumParams a) {
 }
 }  // namespace accum
 
+// Adaptive accumulation passes (kKindAdapt): the accumulation kernels' twins
+// with trace_body's kAdapt changes, one per (search, step, mesh) an
+// accumulation pass can run, at the same workgroup size and waves per SIMD.
+namespace adapt {
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCorner>
+__global__ __launch_bounds__(trace_threads(kLds, kMesh, 0))
+__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, 0), 8)))
+void trace_kernel(AdaptParams a) {
+    static_assert(!kCorner || (kBvh && kLds && kMesh == 0), "corner records: sphere-only LDS kernels");
+    trace_body<kBvh, kLds, kStep, kMesh, false, false, kCorner, false, true>(a.p, a.image, AccumTail{}, a.tail);
+}
+}  // namespace adapt
+
 // ------------------------------------------------------------ resolve kernel
 // Sums each pixel's samples in order (common.rs:333-341), gamma + `as u8`
 // (:344-356), one RGBA8 word per pixel.  The slab is planar and pixel-major,
@@ -2084,15 +2234,16 @@ __global__ __launch_bounds__(kResolveWaves * 64) void resolve_kernel(
 }  // namespace
 
 // ------------------------------------------------------------ the instances
-// Every trace_kernel / corner::trace_kernel / accum::trace_kernel instance is
+// Every trace_kernel / corner::trace_kernel / accum:: / adapt::trace_kernel instance is
 // spelled here and nowhere else: launches, occupancy queries and the LDS opt-in
 // look it up by its TraceVariant (render.h).
 struct TraceInstance {
     const void *fn;    // nullptr: no such instance
     uint32_t threads;  // per workgroup (the kernel's __launch_bounds__)
-    bool corner;       // takes CornerParams (kKindAccum: AccumParams, whatever the search)
+    bool corner;       // takes CornerParams (kKindAccum: AccumParams, kKindAdapt: AdaptParams,
+                       // whatever the search)
 };
-constexpr int kTraceKinds = 4;
+constexpr int kTraceKinds = 5;
 constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds;  // search x step x mesh x kind
 constexpr int trace_index(TraceVariant v) {
     return ((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind;
@@ -2102,9 +2253,10 @@ template <int kI>
 static TraceInstance trace_instance_at() {
     constexpr int kSearch = kI / (8 * kTraceKinds), kMesh = kI / kTraceKinds % 4, kKind = kI % kTraceKinds;
     constexpr bool kStep = kI / (4 * kTraceKinds) % 2 != 0, kCount = kKind == kKindCounting,
-                   kSerial = kKind == kKindSerial, kAccum = kKind == kKindAccum;
+                   kSerial = kKind == kKindSerial, kAccum = kKind == kKindAccum, kAdapt = kKind == kKindAdapt;
     // (an accumulation pass runs at its lean twin's workgroup size)
-    constexpr uint32_t threads = trace_threads(kSearch >= kSearchLdsBox, kMesh, kAccum ? (int)kKindLean : kKind);
+    constexpr uint32_t threads =
+        trace_threads(kSearch >= kSearchLdsBox, kMesh, kAccum || kAdapt ? (int)kKindLean : kKind);
     if constexpr (kSerial && kMesh == 3) {  // the SERIAL passes keep the binary triangle walk
         return {nullptr, 0, false};
     } else if constexpr (kAccum && kSearch != kSearchLdsCorner) {
@@ -2114,6 +2266,14 @@ static TraceInstance trace_instance_at() {
     } else if constexpr (kAccum && kMesh == 0) {
         return {reinterpret_cast<const void *>(&accum::trace_kernel<true, true, kStep, 0, true>), threads, true};
     } else if constexpr (kAccum) {
+        return {nullptr, 0, false};
+    } else if constexpr (kAdapt && kSearch != kSearchLdsCorner) {
+        return {reinterpret_cast<const void *>(
+                    &adapt::trace_kernel<kSearch != kSearchBrute, kSearch == kSearchLdsBox, kStep, kMesh, false>),
+                threads, true};
+    } else if constexpr (kAdapt && kMesh == 0) {
+        return {reinterpret_cast<const void *>(&adapt::trace_kernel<true, true, kStep, 0, true>), threads, true};
+    } else if constexpr (kAdapt) {
         return {nullptr, 0, false};
     } else if constexpr (kSearch != kSearchLdsCorner) {
         return {reinterpret_cast<const void *>(
@@ -2166,6 +2326,18 @@ hipError_t launch_trace_accum(const TraceParams &p, uint32_t blocks, hipStream_t
     // (the passes resolve in-kernel: without a ring the samples would go to the slab)
     if (k.fn == nullptr || p.ring == nullptr || tail.sums == nullptr) return hipErrorInvalidValue;
     AccumParams ap{p, v.search == kSearchLdsCorner ? corner : nullptr, tail};
+    void *args[] = {(void *)&ap};
+    return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
+}
+
+hipError_t launch_trace_adapt(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
+                              const AdaptTail &tail) {
+    const TraceVariant v = trace_variant(p, corner != nullptr, kKindAdapt);
+    const TraceInstance &k = trace_instance(trace_index(v));
+    if (k.fn == nullptr || p.ring == nullptr || tail.sums == nullptr || tail.sumsq == nullptr ||
+        tail.list == nullptr)
+        return hipErrorInvalidValue;
+    AdaptParams ap{p, v.search == kSearchLdsCorner ? corner : nullptr, tail};
     void *args[] = {(void *)&ap};
     return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
 }

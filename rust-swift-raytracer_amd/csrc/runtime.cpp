@@ -718,7 +718,9 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // launch_trace runs the counting kind iff p.stats (set below), the SERIAL instances for sp
     // (an accumulation pass: its own kind, which has no counting twin -- a timed
     // pass gets its HIP-event times and schedule, the work counters stay 0)
-    const int ctv = sp ? kKindSerial : ap ? kKindAccum : timed ? kKindCounting : kKindLean;
+    // (an adaptive pass: the accumulation kernels' twins that take their pixels from a list)
+    const bool adapt = ap && ap->list != nullptr;
+    const int ctv = sp ? kKindSerial : adapt ? kKindAdapt : ap ? kKindAccum : timed ? kKindCounting : kKindLean;
     const TraceVariant tv = trace_variant(p, corner_img != nullptr, ctv);
     if (ap && d->occupancy(tv) == 0) {
         int blocks = 0;
@@ -870,10 +872,24 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         // the first pass (after creation or a reset) starts every fold from 0.0f
         if (ap->n0 == 0) HIP_TRY(hipMemsetAsync(acc.sums, 0, 3 * width * height * sizeof(float), s));
         tail = AccumTail{acc.sums, ap->n0, acc.stride};
+        if (adapt && ap->n0 == 0) {
+            // ... and an adaptive one with zero counts and every pixel listed
+            HIP_TRY(hipMemsetAsync(acc.sumsq, 0, width * height * sizeof(float), s));
+            HIP_TRY(hipMemsetAsync(acc.count, 0, width * height * sizeof(uint32_t), s));
+            HIP_TRY(launch_adapt_iota(const_cast<uint32_t *>(ap->list), (uint32_t)(width * height), s));
+        }
     }
+    // An adaptive pass enumerates its jobs from the list: the launches are
+    // ranges of list entries (units of one pixel = spp jobs) instead of ranges
+    // of rows (units of jobs_per_row jobs).
+    const size_t units = adapt ? ap->nactive : T;
+    const uint64_t jobs_per_unit = adapt ? spp : jobs_per_row;
+    const size_t units_per_slab =
+        adapt ? (size_t)std::min<uint64_t>(std::max<uint64_t>(1, slab_jobs / spp), std::max<size_t>(units, 1))
+              : rows_per_slab;
     uint32_t nslab = 0;  // (counted frames: event triple per launch)
-    for (size_t r0 = 0; r0 < T; r0 += rows_per_slab, ++nslab) {
-        const size_t rows = std::min(rows_per_slab, T - r0);
+    for (size_t r0 = 0; r0 < units; r0 += units_per_slab, ++nslab) {
+        const size_t rows = std::min(units_per_slab, units - r0);
         hipEvent_t *ev3 = nullptr;
         if (timed) {
             while (d->tev.size() < 3 * (size_t)(nslab + 1)) {
@@ -883,15 +899,15 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
             }
             ev3 = &d->tev[3 * (size_t)nslab];
         }
-        const uint64_t njobs = rows * jobs_per_row;
-        p.slab_row0 = (uint32_t)r0;
+        const uint64_t njobs = rows * jobs_per_unit;
+        p.slab_row0 = adapt ? 0u : (uint32_t)r0;
         p.gj32 = nranks == 1 && (uint64_t)width * height * spp < (1ull << 32) ? 1u : 0u;
         p.gj_c0 = (uint32_t)(((uint64_t)height - 1 - r0) * width * spp);
         p.gj_2p = (uint32_t)(2ull * width * spp);
         // (accumulation: jobs at the accumulator's stride, render.h AccumTail)
         if (ap) p.gj32 = (uint64_t)width * height * ap->acc->stride < (1ull << 32) ? 1u : 0u;
         p.njobs = (uint32_t)njobs;
-        p.npix = (uint32_t)(rows * width);
+        p.npix = adapt ? (uint32_t)rows : (uint32_t)(rows * width);
         if (timed) HIP_TRY(hipEventRecord(ev3[0], s));
         if (njobs) {
             const LaunchPlan lp = plan(ctv, njobs);
@@ -913,7 +929,10 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
             if (!d->cset_clean[d->cset]) HIP_TRY(hipMemsetAsync(cur, 0, parts * 128, s));
             p.job_counter = cur;
             p.job_counter_next = d->counter + (size_t)(d->cset ^ 1u) * kMaxParts * 32;
-            if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, corner_img, tail));
+            if (adapt)
+                HIP_TRY(launch_trace_adapt(p, (uint32_t)blocks, s, corner_img,
+                                           AdaptTail{tail.sums, ap->acc->sumsq, ap->list + r0, tail.n0, tail.stride}));
+            else if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, corner_img, tail));
             else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img));
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
@@ -957,7 +976,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     pd.nrec = nrec;
     pd.nslab = nslab;
     pd.launches = launches;
-    pd.samples = (uint64_t)T * jobs_per_row;
+    pd.samples = (uint64_t)units * jobs_per_unit;
     pd.use_bvh = use_bvh;
     pd.use_tbvh = use_tbvh;
     pd.stream = s;
@@ -1953,6 +1972,10 @@ void accum_release(AccumState *a) {
         if (a->done_stream) (void)hipEventSynchronize(a->done);
         if (a->sums) (void)hipFree(a->sums);
         if (a->replay) (void)hipFree(a->replay);
+        for (void *q : {(void *)a->sumsq, (void *)a->count, (void *)a->frame, (void *)a->list[0],
+                        (void *)a->list[1], (void *)a->keep, (void *)a->totals, (void *)a->d_len})
+            if (q) (void)hipFree(q);
+        if (a->h_len) (void)hipHostFree(a->h_len);
         if (a->done) (void)hipEventDestroy(a->done);
     }
     delete a;
@@ -2049,7 +2072,11 @@ int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t 
     if (rc) return rc;
     hipStream_t s = stream ? stream : d->stream;
     const size_t npix = a.width * a.height;
-    if (!d_out) {  // (the kernels always write the frame)
+    // (an adaptive accumulator's passes write its own frame, which is copied out below)
+    uint32_t *const d_user = d_out;
+    if (a.adaptive) {
+        d_out = a.frame;
+    } else if (!d_out) {  // (the kernels always write the frame)
         HIP_TRY(grow(d->out, d->out_cap, npix));
         d_out = d->out;
     }
@@ -2070,13 +2097,43 @@ int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t 
     while (left) {
         const uint32_t n = std::min<uint32_t>(left, 4096u);
         o.samples_per_pixel = (int32_t)n;
-        const AccumPass ap{&a, a.held};
+        AccumPass ap{&a, a.held};
+        if (a.adaptive) {
+            if (a.held == 0) {  // (render_frame fills the list and zeroes the planes)
+                a.cur = 0;
+                a.nactive = (uint32_t)npix;
+            }
+            // an empty list: nothing is traced and N stays (the frame is still delivered)
+            if (a.nactive == 0) break;
+            ap.list = a.list[a.cur];
+            ap.nactive = a.nactive;
+        }
         RtRenderStats st{};
         rc = render_frame(w, cam, a.width, a.height, o, d_out, s, stats ? &st : nullptr, nullptr, a.replay, false,
                           &ap);
         if (rc) return rc;
         a.held += n;
         left -= n;
+        if (a.adaptive) {
+            // the pass's decision: counts, and from min_samples
+            // on the converged pixels leave the list; the new length is read
+            // back, so the host waits for the pass here
+            const bool decide = a.held >= a.min_samples;
+            HIP_TRY(launch_adapt_select(a.list[a.cur], a.nactive, a.sums, a.sumsq, npix, a.count, a.keep, a.held,
+                                        1.0f / (float)a.held, a.tolerance, a.bias, decide, s));
+            if (decide) {
+                HIP_TRY(launch_adapt_compact(a.list[a.cur], a.keep, a.nactive, a.totals, a.list[a.cur ^ 1u], a.d_len,
+                                             s));
+                HIP_TRY(hipMemcpyAsync(a.h_len, a.d_len, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            }
+            HIP_TRY(hipEventRecord(a.done, s));
+            a.done_stream = s;
+            if (decide) {
+                HIP_TRY(hipStreamSynchronize(s));
+                a.cur ^= 1u;
+                a.nactive = *a.h_len;
+            }
+        }
         if (stats) {
             const uint64_t samples = total.samples + st.samples;
             const double ms = total.trace_ms + st.trace_ms, rms = total.resolve_ms + st.resolve_ms;
@@ -2089,6 +2146,11 @@ int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t 
         }
     }
     if (stats) *stats = total;
+    if (a.adaptive) {
+        // (a call that traced nothing still orders the copies after the last pass)
+        if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
+        if (d_user) HIP_TRY(hipMemcpyAsync(d_user, a.frame, npix * 4, hipMemcpyDeviceToDevice, s));
+    }
     if (host_out) {
         HIP_TRY(hipMemcpyAsync(host_out, d_out, npix * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -2134,6 +2196,115 @@ int accum_reset(AccumState &a) {
     std::lock_guard<std::recursive_mutex> lock(wp->mu);
     a.held = 0;
     return 0;
+}
+
+// ------------------------------------------------------------ adaptive accumulation
+// (rt_adapt_*: DESIGN.md 5.7)
+namespace {
+// the accumulator's world, locked, after the reset rule; nullptr with the error set
+WorldState *adapt_begin(AccumState &a, const CameraModel &cam, std::unique_lock<std::recursive_mutex> &lock) {
+    WorldState *wp = accum_world(a);
+    if (!wp) return nullptr;
+    lock = std::unique_lock<std::recursive_mutex>(wp->mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, *wp, cf);
+    return wp;
+}
+}  // namespace
+
+int adapt_enable(AccumState &a, const CameraModel &cam, float tolerance, float bias, uint32_t min_samples) {
+    // (the options were checked by rt_adapt_enable, before the accumulator)
+    std::unique_lock<std::recursive_mutex> lock;
+    WorldState *wp = adapt_begin(a, cam, lock);
+    if (!wp) return -1;
+    if (a.held != 0) {
+        set_error("rt_adapt_enable: the accumulator holds " + std::to_string(a.held) + " samples (reset it first)");
+        return -1;
+    }
+    if (!a.frame) {
+        HIP_TRY(hipSetDevice(a.device));
+        const size_t npix = a.width * a.height;
+        // (an enable that failed half way keeps what it got: the next one goes on, release frees it)
+        auto alloc = [](auto *&q, size_t bytes) { return q ? hipSuccess : hipMalloc((void **)&q, bytes); };
+        HIP_TRY(alloc(a.sumsq, npix * sizeof(float)));
+        HIP_TRY(alloc(a.count, npix * sizeof(uint32_t)));
+        HIP_TRY(alloc(a.list[0], npix * sizeof(uint32_t)));
+        HIP_TRY(alloc(a.list[1], npix * sizeof(uint32_t)));
+        HIP_TRY(alloc(a.keep, npix * sizeof(uint32_t)));
+        HIP_TRY(alloc(a.totals, adapt_compact_blocks(npix) * sizeof(uint32_t)));
+        HIP_TRY(alloc(a.d_len, sizeof(uint32_t)));
+        if (!a.h_len) HIP_TRY(hipHostMalloc((void **)&a.h_len, sizeof(uint32_t)));
+        HIP_TRY(alloc(a.frame, npix * sizeof(uint32_t)));  // (last: its presence means all are)
+    }
+    a.adaptive = true;
+    a.tolerance = tolerance;
+    a.bias = bias;
+    a.min_samples = min_samples;
+    return 0;
+}
+
+int adapt_disable(AccumState &a, const CameraModel &cam) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    if (a.held != 0) {
+        set_error("rt_adapt_disable: the accumulator holds " + std::to_string(a.held) + " samples (reset it first)");
+        return -1;
+    }
+    a.adaptive = false;
+    return 0;
+}
+
+long adapt_active(AccumState &a, const CameraModel &cam) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    return a.adaptive && a.held != 0 ? (long)a.nactive : (long)(a.width * a.height);
+}
+
+namespace {
+// one adaptive plane (4-byte elements) to the host; all zero with no samples held
+int adapt_read_plane(AccumState &a, const CameraModel &cam, bool counts, void *out, const char *who) {
+    if (!out) { set_error(std::string(who) + ": null output"); return -1; }
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!a.adaptive) { set_error(std::string(who) + ": the accumulator is not adaptive"); return -1; }
+    const size_t npix = a.width * a.height;
+    if (a.held == 0) {
+        std::memset(out, 0, npix * 4);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(a.device));
+    HIP_TRY(hipEventSynchronize(a.done));
+    HIP_TRY(hipMemcpy(out, counts ? (const void *)a.count : (const void *)a.sumsq, npix * 4,
+                      hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // namespace
+
+int adapt_read_counts(AccumState &a, const CameraModel &cam, uint32_t *counts) {
+    return adapt_read_plane(a, cam, true, counts, "rt_adapt_read_counts");
+}
+
+int adapt_read_sumsq(AccumState &a, const CameraModel &cam, float *sumsq) {
+    return adapt_read_plane(a, cam, false, sumsq, "rt_adapt_read_sumsq");
+}
+
+long adapt_read_active(AccumState &a, const CameraModel &cam, uint32_t *list, size_t cap) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!a.adaptive) { set_error("rt_adapt_read_active: the accumulator is not adaptive"); return -1; }
+    const size_t npix = a.width * a.height;
+    if (a.held == 0) {  // (every pixel, ascending: what the next pass starts from)
+        for (size_t i = 0; list && i < std::min(cap, npix); ++i) list[i] = (uint32_t)i;
+        return (long)npix;
+    }
+    const size_t n = std::min<size_t>(cap, a.nactive);
+    if (list && n) {
+        HIP_TRY(hipSetDevice(a.device));
+        HIP_TRY(hipEventSynchronize(a.done));
+        HIP_TRY(hipMemcpy(list, a.list[a.cur], n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return (long)a.nactive;
 }
 
 }  // namespace rtamd

@@ -115,8 +115,11 @@ struct DeviceState {
     // 0 until then; same workgroup size, LDS request and waves per SIMD as the
     // lean twin the set-up's decisions were made with)
     int accum_blocks_per_cu[4][2] = {};
+    int adapt_blocks_per_cu[4][2] = {};  // (kKindAdapt, likewise)
     int &occupancy(TraceVariant v) {
-        return v.kind == kKindAccum ? accum_blocks_per_cu[v.search][v.step] : blocks_per_cu[v.search][v.kind][v.step];
+        return v.kind == kKindAdapt   ? adapt_blocks_per_cu[v.search][v.step]
+               : v.kind == kKindAccum ? accum_blocks_per_cu[v.search][v.step]
+                                      : blocks_per_cu[v.search][v.kind][v.step];
     }
     int num_cus = 0;
     // a counted frame's timing events (3 per launch: start, trace end, resolve
@@ -196,13 +199,34 @@ struct AccumState {
     uint32_t *replay = nullptr;   // REPLAY: width * height * stride start states
     hipEvent_t done = nullptr;    // end of the last pass ...
     hipStream_t done_stream = nullptr;  // ... and the stream it ran on (nullptr: none yet)
+    // Adaptive accumulation (rt_adapt_enable): the pixels still
+    // sampled are those of list[cur] (frame indices, ascending), nactive of
+    // them, all holding `held` samples; the others stopped at count[pixel].
+    // Everything below is allocated by adapt_enable and freed with the sums.
+    bool adaptive = false;
+    float tolerance = 0.0f, bias = 0.0f;
+    uint32_t min_samples = 0;
+    float *sumsq = nullptr;       // width * height: the fold of y y, y = (r + g) + b
+    uint32_t *count = nullptr;    // width * height: samples each pixel holds
+    uint32_t *frame = nullptr;    // width * height RGBA8: frozen pixels keep their last pass's bytes
+    uint32_t *list[2] = {nullptr, nullptr};  // two lists alternate (the compaction's input and output)
+    uint32_t cur = 0;
+    uint32_t nactive = 0;         // entries of list[cur] (meaningful while held != 0)
+    uint32_t *keep = nullptr;     // width * height flags of the last decision
+    uint32_t *totals = nullptr;   // the compaction's block totals
+    uint32_t *d_len = nullptr;    // the new list length on the device ...
+    uint32_t *h_len = nullptr;    // ... and in pinned host memory
 };
 
 // One pass of an accumulation, for render_frame: n0 samples held, the frame's
-// o.samples_per_pixel more are traced (1..4096).
+// o.samples_per_pixel more are traced (1..4096).  list (adaptive accumulators):
+// the pass traces only the nactive pixels listed, with the adaptive instances;
+// d_out is then the accumulator's own frame.
 struct AccumPass {
     AccumState *acc;
     uint32_t n0;
+    const uint32_t *list = nullptr;
+    uint32_t nactive = 0;
 };
 
 // One launch of a SERIAL-mode pass (render_frame_serial): the frame's jobs are
@@ -259,6 +283,15 @@ long accum_samples(AccumState &a, const CameraModel &cam);
 int accum_read(AccumState &a, const CameraModel &cam, float *sums);
 int accum_reset(AccumState &a);
 void accum_free(AccumState *a);
+// Adaptive accumulation (rt_adapt_*, include/raytracer_amd.h).  enable and
+// disable need an accumulator that holds no samples; the reads wait for the
+// last pass.  read_active returns the list's length (list may be nullptr).
+int adapt_enable(AccumState &a, const CameraModel &cam, float tolerance, float bias, uint32_t min_samples);
+int adapt_disable(AccumState &a, const CameraModel &cam);
+long adapt_active(AccumState &a, const CameraModel &cam);
+int adapt_read_counts(AccumState &a, const CameraModel &cam, uint32_t *counts);
+int adapt_read_sumsq(AccumState &a, const CameraModel &cam, float *sumsq);
+long adapt_read_active(AccumState &a, const CameraModel &cam, uint32_t *list, size_t cap);
 // Waits for device d's pending counted frame and fills stats from it.
 int collect_frame_stats(DeviceState *d, RtRenderStats *stats);
 

@@ -34,6 +34,8 @@ EXPORTS = (
     "rt_world_set_sphere_material", "rt_world_set_triangle_material", "rt_assemble_tiles",
     "rt_accum_default_options", "rt_accum_create", "rt_accum_add", "rt_accum_add_device",
     "rt_accum_samples", "rt_accum_read", "rt_accum_reset", "rt_accum_free",
+    "rt_adapt_default_options", "rt_adapt_enable", "rt_adapt_disable", "rt_adapt_active",
+    "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active",
 )
 
 
@@ -65,6 +67,10 @@ class AccumOptions(C.Structure):
     _fields_ = [("max_ray_bounces", C.c_int32), ("rng_mode", C.c_uint32), ("seed", C.c_uint32),
                 ("replay_states", C.POINTER(C.c_uint32)), ("sample_stride", C.c_uint32),
                 ("device", C.c_int32), ("accel", C.c_int32)]
+
+
+class AdaptOptions(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("bias", C.c_float), ("min_samples", C.c_uint32)]
 
 
 class RenderStats(C.Structure):
@@ -178,6 +184,20 @@ def lib(path=None):
             L.rt_accum_reset.restype = C.c_int
             L.rt_accum_reset.argtypes = [C.c_void_p]
             L.rt_accum_free.argtypes = [C.c_void_p]
+        if hasattr(L, "rt_adapt_enable"):  # (likewise)
+            L.rt_adapt_default_options.argtypes = [C.POINTER(AdaptOptions)]
+            L.rt_adapt_enable.restype = C.c_int
+            L.rt_adapt_enable.argtypes = [C.c_void_p, C.POINTER(AdaptOptions)]
+            L.rt_adapt_disable.restype = C.c_int
+            L.rt_adapt_disable.argtypes = [C.c_void_p]
+            L.rt_adapt_active.restype = C.c_long
+            L.rt_adapt_active.argtypes = [C.c_void_p]
+            L.rt_adapt_read_counts.restype = C.c_int
+            L.rt_adapt_read_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.rt_adapt_read_sumsq.restype = C.c_int
+            L.rt_adapt_read_sumsq.argtypes = [C.c_void_p, fp]
+            L.rt_adapt_read_active.restype = C.c_long
+            L.rt_adapt_read_active.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t]
         _libs[path] = L
     return _libs[path]
 
@@ -431,6 +451,49 @@ class Accumulator:
 
     def reset(self):
         self._check(self._L.rt_accum_reset(self._a), "rt_accum_reset")
+
+    # ---- adaptive accumulation (rt_adapt_*)
+    def set_adaptive(self, tolerance=None, bias=None, min_samples=None, enable=True):
+        """rt_adapt_enable with the defaults overridden (enable=False: rt_adapt_disable);
+        the accumulator must hold no samples."""
+        if not enable:
+            self._check(self._L.rt_adapt_disable(self._a), "rt_adapt_disable")
+            return
+        o = AdaptOptions()
+        self._L.rt_adapt_default_options(C.byref(o))
+        if tolerance is not None:
+            o.tolerance = tolerance
+        if bias is not None:
+            o.bias = bias
+        if min_samples is not None:
+            o.min_samples = min_samples
+        self._check(self._L.rt_adapt_enable(self._a, C.byref(o)), "rt_adapt_enable")
+
+    @property
+    def active(self):
+        """Pixels still sampled (width * height with no samples held or when not adaptive)."""
+        return int(self._check(self._L.rt_adapt_active(self._a), "rt_adapt_active"))
+
+    def counts(self):
+        """Samples each pixel holds: uint32[height, width], top row first."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.rt_adapt_read_counts(self._a, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                    "rt_adapt_read_counts")
+        return out
+
+    def sumsq(self):
+        """The fold of y * y, y = (r + g) + b: float32[height, width], top row first."""
+        out = np.zeros((self.height, self.width), np.float32)
+        self._check(self._L.rt_adapt_read_sumsq(self._a, out.ctypes.data_as(C.POINTER(C.c_float))),
+                    "rt_adapt_read_sumsq")
+        return out
+
+    def active_list(self):
+        """The active list: uint32 frame indices (row * width + col, top row first), ascending."""
+        out = np.zeros(self.width * self.height, np.uint32)
+        n = self._check(self._L.rt_adapt_read_active(self._a, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size),
+                        "rt_adapt_read_active")
+        return out[:n].copy()
 
 
 def write_ppm(rgba: np.ndarray, path: str):
