@@ -199,12 +199,15 @@ static void check_cells(const SceneModel &s, const TriangleCells &tc, const Tria
     for (const Triangle &t : s.triangles)
         for (const Vec3 &v : {t.v0, t.v1, t.v2}) {
             const double c[3] = {v.x, v.y, v.z};
+            // (the grid is laid over the finite vertices and centres: a ray that
+            // starts outside it walks the static tree)
+            if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) continue;
             for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], c[k]); hi[k] = std::max(hi[k], c[k]); }
         }
     for (int k = 0; k < 3; ++k) ext = std::max(ext, hi[k] - lo[k]);
     for (const Sphere &sp : s.spheres) {
         const double r = std::fabs((double)sp.radius), c[3] = {sp.center.x, sp.center.y, sp.center.z};
-        if (!(r <= ext)) continue;
+        if (!(r <= ext) || !(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]))) continue;
         for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], c[k] - r); hi[k] = std::max(hi[k], c[k] + r); }
     }
     for (int k = 0; k < 3; ++k)

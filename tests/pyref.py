@@ -27,6 +27,8 @@ np.seterr(all="ignore")
 def dec_to_f32(lit: str) -> np.float32:
     """Correctly rounded decimal -> binary32 (Rust `str::parse::<f32>`)."""
     q = Fraction(lit)
+    if abs(q) >= 2 ** 128 - 2 ** 103:  # at or past the midpoint above f32::MAX: infinite
+        return F(np.inf) if q > 0 else F(-np.inf)
     c = F(float(q))  # may be off by one ulp through double rounding
     best = None
     for cand in (np.nextafter(c, F(-np.inf)), c, np.nextafter(c, F(np.inf))):
