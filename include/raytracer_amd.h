@@ -326,6 +326,14 @@ long rt_adapt_read_active(RtAccum *acc, uint32_t *list, size_t cap);
  * floats copied or a negative error. */
 long rt_read_samples(const Rust_WorldHandle *handle, int device, float *out, size_t n);
 
+/* Diagnostics: how the LAST frame trace launch on `device` (-1 = current)
+ * tested the sphere tree's leaves.  0: each lane tested a leaf where its walk
+ * entered it.  C >= 2: the walk recorded entered leaves, at most C per lane,
+ * and the wave tested them in shared passes (the lean
+ * corner-record kernel, RT_AMD_LEAF_DEFER=0 turns it off).  Both give
+ * bit-identical frames.  Negative: an error. */
+int rt_leaf_defer(const Rust_WorldHandle *handle, int device);
+
 /* Frees a handle from load_world (the reference never frees, lib.rs:42-45). */
 void rt_free_world(Rust_WorldHandle *handle);
 

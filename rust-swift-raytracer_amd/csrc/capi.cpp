@@ -200,6 +200,14 @@ int rt_render_device(const Rust_WorldHandle *h, size_t width, size_t height,
                                static_cast<hipStream_t>(hip_stream), stats);
 }
 
+int rt_leaf_defer(const Rust_WorldHandle *h, int device) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_leaf_defer: null argument");
+        return -1;
+    }
+    return rtamd::leaf_defer(h->world->state, device);
+}
+
 long rt_read_samples(const Rust_WorldHandle *h, int device, float *out, size_t n) {
     if (!h || !h->world || !out) {
         rtamd::set_error("rt_read_samples: null argument");

@@ -220,40 +220,52 @@ inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : 
 //           from a list)
 enum : int { kSearchBrute = 0, kSearchGlobal = 1, kSearchLdsBox = 2, kSearchLdsCorner = 3 };
 enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2, kKindAccum = 3, kKindAdapt = 4 };
+//   defer:  the corner walk defers its leaf tests to shared leaf passes
+//           (DESIGN.md 5.2 "deferred leaves")
 struct TraceVariant {
     int search;
     bool step;
     int mesh;
     int kind;
+    bool defer = false;
     bool lds() const { return search >= kSearchLdsBox; }
 };
 // The instance that serves a scene of family `mesh` (0-3) searched as `search`:
 // the SERIAL passes keep the binary triangle walk and the box records, and the
 // corner records exist for sphere-only scenes.  The one place these rules live.
-inline TraceVariant trace_variant(int search, bool step, int mesh, int kind) {
+// defer: deferred leaf tests are wanted (RT_AMD_LEAF_DEFER, on by default).  Only
+// the lean whole-walk corner kernel has them: the counting kernel keeps the
+// immediate walk (its counters describe that walk), and so do the sliced
+// walks and the accumulation kinds.
+inline TraceVariant trace_variant(int search, bool step, int mesh, int kind, bool defer = false) {
     if (kind == kKindSerial && mesh == 3) mesh = 2;
     if (search == kSearchLdsCorner && (mesh != 0 || kind == kKindSerial)) search = kSearchLdsBox;
-    return TraceVariant{search, step, mesh, kind};
+    defer = defer && search == kSearchLdsCorner && !step && mesh == 0 && kind == kKindLean;
+    return TraceVariant{search, step, mesh, kind, defer};
 }
 // ... and the one a launch with these parameters runs as kernel kind `kind`;
 // corner: the corner records are passed (launch_trace)
-inline TraceVariant trace_variant(const TraceParams &p, bool corner, int kind) {
+inline TraceVariant trace_variant(const TraceParams &p, bool corner, int kind, bool defer = false) {
     const int mesh = trace_mesh_kind(p.ntri != 0, p.tnodes != 0);
     const int search = !p.nnodes ? kSearchBrute : !p.use_lds ? kSearchGlobal : corner ? kSearchLdsCorner : kSearchLdsBox;
-    return trace_variant(search, p.step != 0, mesh == 2 && p.tw_nodes != nullptr ? 3 : mesh, kind);
+    return trace_variant(search, p.step != 0, mesh == 2 && p.tw_nodes != nullptr ? 3 : mesh, kind, defer);
 }
 // Frames rendered without stats run a kind whose work counters compile away
 // (one VALU increment per node / sphere test / ray); SERIAL passes their own.
-inline TraceVariant trace_variant(const TraceParams &p, bool corner) {
-    return trace_variant(p, corner, p.mode >= kRngSerialCount ? kKindSerial : p.stats ? kKindCounting : kKindLean);
+inline TraceVariant trace_variant(const TraceParams &p, bool corner, bool defer) {
+    return trace_variant(p, corner, p.mode >= kRngSerialCount ? kKindSerial : p.stats ? kKindCounting : kKindLean,
+                         defer);
 }
 
 // corner (sphere-only frames with p.use_lds): the corner records (bvh.h
 // SphereBVH::corner, 8 uint4 per node) the workgroups stage instead of the box
 // records (the corner-record kernel instances; trace_corner_lds bytes each).
-// Runs instance trace_variant(p, corner != nullptr).
+// Runs instance trace_variant(p, corner != nullptr, defer).
 hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream,
-                        const uint4 *corner = nullptr);
+                        const uint4 *corner = nullptr, bool defer = false);
+// Pending leaves per lane of instance v's deferred walk; 0: it tests leaves
+// where it enters them.
+int trace_leaf_defer(TraceVariant v);
 // One pass of a progressive accumulation: the frame launch p
 // (p.spp = the pass's samples per pixel n, fused resolve, one rank) as instance
 // trace_variant(p, corner != nullptr, kKindAccum).  Sample s of the pass at

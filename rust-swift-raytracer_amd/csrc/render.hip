@@ -380,8 +380,11 @@ __device__ __forceinline__ bool sphere_node(const BvhView &v, F3 inv, uint32_t o
 // exceeds the near one (DESIGN.md 5.2 point 4), so min and max would pick the
 // same two values.  v_max3 / v_min3 drop a NaN operand like fminf / fmaxf do
 // and give NaN when all three are, which no compare below takes for a skip.
+// tn_out, lw_out (the deferred walk records them for a leaf it enters): the
+// box's t_near, which the third skip condition compared, and the link word.
 __device__ __forceinline__ bool sphere_node_corner(uint32_t offn, uint32_t offf, F3 inv, float best_t, F3 nn,
-                                                   F3 nf, uint32_t &node, uint32_t &leaf, uint32_t &node_tests) {
+                                                   F3 nf, uint32_t &node, uint32_t &leaf, uint32_t &node_tests,
+                                                   float &tn_out, uint32_t &lw_out, bool &any_leaf) {
     ++node_tests;
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef float f3v __attribute__((ext_vector_type(3)));
@@ -405,13 +408,32 @@ __device__ __forceinline__ bool sphere_node_corner(uint32_t offn, uint32_t offf,
     const bool is_leaf = (int32_t)lw < 0;
     node = (skip || is_leaf) ? (lw & 0xFFFFu) : (lw >> 16);
     leaf = (lw >> 16) & 0x7FFFu;
+    tn_out = tn;
+    lw_out = lw;
+    // (whether some lane of the wave enters a leaf, from ballots of the
+    // compares themselves: each is the compare's own result mask, no VALU.
+    // max(tn, 0.001) > tf is `tn > tf || tf < 0.001f`, NaN operands included:
+    // the form the compiler gives the first two skip conditions anyway)
+    any_leaf = (__builtin_amdgcn_ballot_w64(is_leaf) &
+                ~(__builtin_amdgcn_ballot_w64(fmaxf(tn, 0.001f) > tf) |
+                  __builtin_amdgcn_ballot_w64(__float_as_int(tn) > __float_as_int(best_t)))) != 0;
     return !skip && is_leaf;
 #else
     (void)offn; (void)offf; (void)inv; (void)best_t; (void)nn; (void)nf;
     node = 0xFFFFu;
     leaf = 0;
+    tn_out = 0.0f;
+    lw_out = 0;
+    any_leaf = false;
     return false;
 #endif
+}
+__device__ __forceinline__ bool sphere_node_corner(uint32_t offn, uint32_t offf, F3 inv, float best_t, F3 nn,
+                                                   F3 nf, uint32_t &node, uint32_t &leaf, uint32_t &node_tests) {
+    float tn;
+    uint32_t lw;
+    bool any_leaf;
+    return sphere_node_corner(offn, offf, inv, best_t, nn, nf, node, leaf, node_tests, tn, lw, any_leaf);
 }
 
 // The corner walk's first node (an index): the root's near child for the
@@ -1225,11 +1247,28 @@ struct AdaptParams {
     const uint4 *image;
     AdaptTail tail;
 };
+// kDefer (the lean whole-walk corner kernel only): the corner walk records
+// the leaves it enters, at most kDefer per lane, and the wave tests them in
+// shared leaf passes (DESIGN.md 5.2 "deferred leaves"); 0: each lane tests a
+// leaf where it enters it.
+#ifndef RT_LEAF_DEFER_C
+#define RT_LEAF_DEFER_C 2  // pending leaves per lane (2 or 3)
+#endif
+#ifndef RT_LEAF_RECULL
+#define RT_LEAF_RECULL 0  // 1: drop a pending leaf whose stored t_near now exceeds best_t (A/B: slower)
+#endif
+constexpr int kLeafDeferC = RT_LEAF_DEFER_C;
+constexpr bool kLeafRecull = RT_LEAF_RECULL != 0;
+static_assert(kLeafDeferC == 2 || kLeafDeferC == 3, "pending leaves per lane: 2 or 3");
 template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner,
-          bool kAccum = false, bool kAdapt = false>
+          bool kAccum = false, bool kAdapt = false, int kDefer = 0>
 __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, AccumTail tail = AccumTail{},
                                            AdaptTail xtail_arg = AdaptTail{}) {
     static_assert(!(kAccum && kAdapt), "an adaptive pass is an instance of its own");
+#ifndef RT_COUNT_DEFER  // (diagnostic build: the counting corner instance with the deferred walk)
+    static_assert(kDefer == 0 || (kCorner && !kCount && !kStep && !kSerial && kMesh == 0),
+                  "deferred leaves: the lean whole-walk corner kernel");
+#endif
     // SERIAL count passes: the walk of the previous pass set the first sample
     // and this iteration's candidates per sample (ctrl[5], <= the launch's K)
     if (kSerial && p.ctrl != nullptr) {
@@ -1514,6 +1553,55 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     F3 nn, nf;
                     sphere_corner_slabs(org, inv, sph_inflation(p, bnd, best_t), oct, nn, nf);
                     const uint32_t offn = sph_root + 16u * oct, offf = sph_root + 112u - 16u * oct;
+                    if (kDefer != 0) {
+                        // Deferred leaves: a lane that enters a leaf records it
+                        // and walks on; the walking lanes test their recorded
+                        // leaves together once one of them holds kDefer, and
+                        // the whole wave tests what is left when no lane can
+                        // step (a lane whose walk ended keeps its entries until
+                        // then).  `pend` holds the upper halves of the leaves'
+                        // link words (kCornerLeaf | leaf word) in 16-bit fields,
+                        // the latest lowest; 0 = no entry.  tnr[r]: entry r's
+                        // t_near.
+                        typedef typename std::conditional<(kDefer > 2), uint64_t, uint32_t>::type Pend;
+                        Pend pend = 0;
+                        float tnr[kDefer > 0 ? kDefer : 1];
+                        // every lane's r-th entry in one pass.  An entry whose box
+                        // now begins beyond best_t is dropped (the node step's
+                        // third skip condition, with the best_t of now)
+                        auto flush = [&]() {
+#pragma unroll
+                            for (int r = 0; r < kDefer; ++r) {
+                                const uint32_t ent = (uint32_t)(pend >> 16 * r) & 0xFFFFu;
+                                if (ent != 0u &&
+                                    !(kLeafRecull && __float_as_int(tnr[r]) > __float_as_int(best_t)))
+                                    sphere_leaf<true>(view, org, dir, ent & 0x7FFFu, best_t, best_i, sph_tests);
+                            }
+                            pend = 0;
+                        };
+                        do {
+                            uint32_t leaf, lw;
+                            float tn;
+                            bool any_leaf;
+                            const bool lf = sphere_node_corner(offn, offf, inv, best_t, nn, nf, node, leaf,
+                                                               node_tests, tn, lw, any_leaf);
+                            // (both branches wave-uniform, on masks the compares
+                            // produce: a trip in which no lane enters a leaf runs
+                            // the immediate walk's VALU)
+                            if (any_leaf) {
+                                if (lf) {
+                                    pend = pend << 16 | (lw >> 16);
+                                    if (kLeafRecull) {
+#pragma unroll
+                                        for (int r = kDefer - 1; r > 0; --r) tnr[r] = tnr[r - 1];
+                                        tnr[0] = tn;
+                                    }
+                                }
+                                if (__builtin_amdgcn_ballot_w64((pend >> 16 * (kDefer - 1)) != 0) != 0) flush();
+                            }
+                        } while (node != 0xFFFFu);
+                        flush();
+                    } else
                     do {
                         uint32_t leaf;
                         if (sphere_node_corner(offn, offf, inv, best_t, nn, nf, node, leaf, node_tests))
@@ -2135,6 +2223,18 @@ void trace_kernel(CornerParams c) {
     static_assert(kBvh && kLds && kMesh == 0 && !kSerial, "corner records: sphere-only LDS frame kernels");
     trace_body<true, true, kStep, 0, kCount, false, true>(c.p, c.image);
 }
+// The lean whole-walk kernel with deferred leaf tests (trace_body's kDefer):
+// an instance of its own beside the immediate walk above, which stays the code
+// it was (RT_AMD_LEAF_DEFER=0 runs it).  Same name and parameter list again.
+namespace deferred {
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial = false>
+__global__ __launch_bounds__(trace_threads(true, 0, kCount ? 1 : 0))
+__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(true, 0, kCount ? 1 : 0), 8)))
+void trace_kernel(CornerParams c) {
+    static_assert(kBvh && kLds && !kStep && kMesh == 0 && !kSerial, "deferred leaves: whole corner walks");
+    trace_body<true, true, false, 0, kCount, false, true, false, false, kLeafDeferC>(c.p, c.image);
+}
+}  // namespace deferred
 }  // namespace corner
 
 // Accumulation passes (kKindAccum): the lean frame kernels' twins with
@@ -2244,20 +2344,28 @@ struct TraceInstance {
                        // whatever the search)
 };
 constexpr int kTraceKinds = 5;
-constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds;  // search x step x mesh x kind
+constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds * 2;  // search x step x mesh x kind x defer
 constexpr int trace_index(TraceVariant v) {
-    return ((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind;
+    return (((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind) * 2 + v.defer;
 }
 
-template <int kI>
+template <int kJ>
 static TraceInstance trace_instance_at() {
+    constexpr int kI = kJ / 2;
+    constexpr bool kDeferred = kJ % 2 != 0;
     constexpr int kSearch = kI / (8 * kTraceKinds), kMesh = kI / kTraceKinds % 4, kKind = kI % kTraceKinds;
     constexpr bool kStep = kI / (4 * kTraceKinds) % 2 != 0, kCount = kKind == kKindCounting,
                    kSerial = kKind == kKindSerial, kAccum = kKind == kKindAccum, kAdapt = kKind == kKindAdapt;
     // (an accumulation pass runs at its lean twin's workgroup size)
     constexpr uint32_t threads =
         trace_threads(kSearch >= kSearchLdsBox, kMesh, kAccum || kAdapt ? (int)kKindLean : kKind);
-    if constexpr (kSerial && kMesh == 3) {  // the SERIAL passes keep the binary triangle walk
+    if constexpr (kDeferred) {  // deferred leaves: the lean whole-walk corner kernel (render.h trace_variant)
+        if constexpr (kSearch == kSearchLdsCorner && !kStep && kMesh == 0 && kKind == kKindLean)
+            return {reinterpret_cast<const void *>(&corner::deferred::trace_kernel<true, true, false, 0, false, false>),
+                    threads, true};
+        else
+            return {nullptr, 0, false};
+    } else if constexpr (kSerial && kMesh == 3) {  // the SERIAL passes keep the binary triangle walk
         return {nullptr, 0, false};
     } else if constexpr (kAccum && kSearch != kSearchLdsCorner) {
         return {reinterpret_cast<const void *>(
@@ -2279,6 +2387,11 @@ static TraceInstance trace_instance_at() {
         return {reinterpret_cast<const void *>(
                     &trace_kernel<kSearch != kSearchBrute, kSearch == kSearchLdsBox, kStep, kMesh, kCount, kSerial>),
                 threads, false};
+#ifdef RT_COUNT_DEFER
+    } else if constexpr (kMesh == 0 && kCount && !kStep) {  // diagnostic build: the deferred walk, counted
+        return {reinterpret_cast<const void *>(&corner::deferred::trace_kernel<true, true, false, 0, true, false>),
+                threads, true};
+#endif
     } else if constexpr (kMesh == 0 && !kSerial) {  // corner records: the sphere-only frame kernels
         return {reinterpret_cast<const void *>(&corner::trace_kernel<true, true, kStep, 0, kCount, false>), threads,
                 true};
@@ -2310,8 +2423,9 @@ size_t trace_dyn_lds(const TraceParams &p, TraceVariant v) {
     return tree + (v.mesh == 3 ? (size_t)p.tw_depth * trace_block_threads(v) * 2u : 0u);
 }
 
-hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner) {
-    const TraceVariant v = trace_variant(p, corner != nullptr);
+hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
+                        bool defer) {
+    const TraceVariant v = trace_variant(p, corner != nullptr, defer);
     const TraceInstance &k = trace_instance(trace_index(v));
     if (k.fn == nullptr) return hipErrorInvalidValue;
     CornerParams cp{p, corner};  // (begins with the TraceParams: either kernel's argument block)
@@ -2346,6 +2460,10 @@ hipError_t trace_occupancy(int *blocks_per_cu, TraceVariant v, size_t lds_bytes)
     const TraceInstance &k = trace_instance(trace_index(v));
     if (k.fn == nullptr) return hipErrorInvalidValue;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, (int)k.threads, lds_bytes);
+}
+
+int trace_leaf_defer(TraceVariant v) {
+    return v.defer && trace_instance(trace_index(v)).fn != nullptr ? kLeafDeferC : 0;
 }
 
 hipError_t trace_lds_opt_in() {

@@ -226,6 +226,16 @@ static int device_for(WorldState &w, int want, DeviceState *&out) {
                         }
                     }
                 if (fits) {
+                    // (the deferred-leaf lean instance, where the build has one)
+                    const TraceVariant v = trace_variant(kSearchLdsCorner, false, tri, kKindLean, true);
+                    if (trace_leaf_defer(v) != 0 &&
+                        (trace_occupancy(&d->occupancy(v), v, corner) != hipSuccess ||
+                         keeps_workgroups(v, corner, fits) != hipSuccess)) {
+                        (void)hipGetLastError();
+                        fits = false;
+                    }
+                }
+                if (fits) {
                     HIP_TRY(hipMalloc((void **)&d->bvh_corner, bv.corner.size() * 4));
                     HIP_TRY(hipMemcpy(d->bvh_corner, bv.corner.data(), bv.corner.size() * 4,
                                       hipMemcpyHostToDevice));
@@ -553,6 +563,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     p.steps = (uint32_t)std::max<uint64_t>(1, env_u64("RT_AMD_STEPS", 128));
     p.row_block = B; p.rank = o.rank; p.nranks = nranks;
     const uint4 *corner_img = nullptr;  // the LDS tree as corner records (sphere-only frames), else box records
+    bool leaf_defer = false;            // ... walked with deferred leaf tests (render.h trace_variant)
     const bool use_bvh = d->nnodes > 0 && o.accel != RT_ACCEL_BRUTE;
     if (use_bvh) {
         const SphereBVH &bv = w.bvh;
@@ -568,6 +579,9 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
         const bool lds_on = env_u64("RT_AMD_LDS", 1) != 0;
         if (lds_on && sp == nullptr && d->corner_bytes > 0 && env_u64("RT_AMD_CORNER", 1) != 0)
             corner_img = d->bvh_corner;
+        // (RT_AMD_LEAF_DEFER=0: the lean corner kernel tests leaves where it
+        // enters them, for A/B runs and tests)
+        leaf_defer = corner_img != nullptr && env_u64("RT_AMD_LEAF_DEFER", 1) != 0;
         p.use_lds = lds_on && (d->lds_bytes > 0 || corner_img != nullptr);
         for (int k = 0; k < 3; ++k) p.bvh_c[k] = bv.centre[k];
         p.bvh_r = bv.radius; p.bvh_rmax = bv.rmax; p.bvh_mag = bv.mag;
@@ -721,7 +735,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // (an adaptive pass: the accumulation kernels' twins that take their pixels from a list)
     const bool adapt = ap && ap->list != nullptr;
     const int ctv = sp ? kKindSerial : adapt ? kKindAdapt : ap ? kKindAccum : timed ? kKindCounting : kKindLean;
-    const TraceVariant tv = trace_variant(p, corner_img != nullptr, ctv);
+    const TraceVariant tv = trace_variant(p, corner_img != nullptr, ctv, leaf_defer);
     if (ap && d->occupancy(tv) == 0) {
         int blocks = 0;
         HIP_TRY(trace_occupancy(&blocks, tv, trace_dyn_lds(p, tv)));
@@ -816,7 +830,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     // workgroups, waves, jobs per queue pull (chunk) and job-queue partitions
     struct LaunchPlan { uint64_t blocks, nwaves, chunk, parts, block_threads; };
     auto plan = [&](int k, uint64_t njobs) -> LaunchPlan {
-        const TraceVariant v = trace_variant(p, corner_img != nullptr, k);
+        const TraceVariant v = trace_variant(p, corner_img != nullptr, k, leaf_defer);
         const uint64_t wpb = trace_block_threads(v) / 64;
         const uint64_t jobs_per_block = wpb * 256;
         uint64_t blocks = std::min<uint64_t>((uint64_t)d->occupancy(v) * d->num_cus,
@@ -933,7 +947,8 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
                 HIP_TRY(launch_trace_adapt(p, (uint32_t)blocks, s, corner_img,
                                            AdaptTail{tail.sums, ap->acc->sumsq, ap->list + r0, tail.n0, tail.stride}));
             else if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, corner_img, tail));
-            else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img));
+            else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img, leaf_defer));
+            d->last_leaf_defer = trace_leaf_defer(tv);
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
             d->cset_clean[d->cset] = true;
@@ -1635,6 +1650,14 @@ int render_frame_serial(WorldState &w, const CameraModel &cam, size_t width, siz
         }
     }
     return 0;
+}
+
+int leaf_defer(WorldState &w, int device) {
+    std::lock_guard<std::recursive_mutex> lock(w.mu);  // (device_for may add a device)
+    DeviceState *d = nullptr;
+    int rc = device_for(w, device, d);
+    if (rc) return rc;
+    return d->last_leaf_defer;
 }
 
 long read_samples(WorldState &w, int device, float *out, size_t n) {

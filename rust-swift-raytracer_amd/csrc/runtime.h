@@ -116,7 +116,9 @@ struct DeviceState {
     // lean twin the set-up's decisions were made with)
     int accum_blocks_per_cu[4][2] = {};
     int adapt_blocks_per_cu[4][2] = {};  // (kKindAdapt, likewise)
+    int defer_blocks_per_cu = 0;         // (the deferred-leaf lean corner instance)
     int &occupancy(TraceVariant v) {
+        if (v.defer) return defer_blocks_per_cu;
         return v.kind == kKindAdapt   ? adapt_blocks_per_cu[v.search][v.step]
                : v.kind == kKindAccum ? accum_blocks_per_cu[v.search][v.step]
                                       : blocks_per_cu[v.search][v.kind][v.step];
@@ -141,6 +143,7 @@ struct DeviceState {
     size_t last_jobs = 0;                                       // jobs of the last launch
     size_t last_spp = 0;                                        // and its spp
     bool last_fused = false;                                    // it resolved in-kernel (no slab)
+    int last_leaf_defer = 0;                                    // its walk's pending leaves per lane (rt_leaf_defer)
     ~DeviceState();
 };
 
@@ -331,6 +334,7 @@ int render_frame_host(WorldState &w, const CameraModel &cam, size_t width, size_
 void prepare_camera(WorldState &w, const CameraModel &cam, bool tree = false);
 
 long read_samples(WorldState &w, int device, float *out, size_t n);
+int leaf_defer(WorldState &w, int device);
 
 size_t tile_rows(size_t height, uint32_t row_block, uint32_t rank, uint32_t nranks);
 size_t tile_row(size_t k, uint32_t row_block, uint32_t rank, uint32_t nranks);

@@ -35,7 +35,7 @@ EXPORTS = (
     "rt_accum_default_options", "rt_accum_create", "rt_accum_add", "rt_accum_add_device",
     "rt_accum_samples", "rt_accum_read", "rt_accum_reset", "rt_accum_free",
     "rt_adapt_default_options", "rt_adapt_enable", "rt_adapt_disable", "rt_adapt_active",
-    "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active",
+    "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active", "rt_leaf_defer",
 )
 
 
@@ -168,6 +168,9 @@ def lib(path=None):
         L.rt_assemble_tiles.restype = C.c_int
         L.rt_assemble_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                         C.c_uint32, C.c_size_t, C.c_void_p]
+        if hasattr(L, "rt_leaf_defer"):  # (an older build loaded for an A/B run has none)
+            L.rt_leaf_defer.restype = C.c_int
+            L.rt_leaf_defer.argtypes = [H, C.c_int]
         if hasattr(L, "rt_accum_create"):  # (an older build loaded for an A/B run has none)
             L.rt_accum_default_options.argtypes = [C.POINTER(AccumOptions)]
             L.rt_accum_create.restype = C.c_void_p
@@ -365,6 +368,14 @@ class World:
         if n < 0:
             raise RenderError(f"rt_read_samples failed ({n}): {self._L.rt_last_error().decode()}")
         return out[: n // 4]
+
+    def leaf_defer(self, device=-1):
+        """rt_leaf_defer: pending leaves per lane of the deferred-leaf walk the
+        last frame trace launch ran (0: it tested leaves where it entered them)."""
+        n = self._L.rt_leaf_defer(self._h, device)
+        if n < 0:
+            raise RenderError(f"rt_leaf_defer failed ({n}): {self._L.rt_last_error().decode()}")
+        return n
 
     def render_device(self, width, height, out_ptr: int, stream_ptr: int = 0, spp=16, depth=8,
                       mode=RNG_COUNTER, seed=DEFAULT_SEED, row_block=8, rank=0, nranks=1,

@@ -231,6 +231,132 @@ static WaveCost wave_cost(const std::vector<std::vector<uint8_t>> &w, bool merge
     return r;
 }
 
+// SIM_WAVE_DEFER: deferred leaf tests (render.hip trace_body kDefer), a true
+// lock-step run of 64 consecutive walks on their own geometry -- deferral
+// changes best_t and with it the cull decisions, so the recorded events do
+// not do.  A lane that enters a leaf records (leaf, t_near) and walks on, at
+// most C entries per lane.  The lanes flush -- test their entries pass by
+// pass, every lane's r-th entry together -- as soon as one of them holds C,
+// and once more when no lane can step.  join = false (the kernel): a lane
+// whose walk has ended keeps its entries until that last flush; join = true:
+// it takes part in every flush.  recull: at the flush an entry whose t_near
+// is now > best_t is dropped untested.  A pass costs like the leaf code as it
+// is (leaf cost x the largest leaf among its lanes + root cost per sphere
+// position at which some lane has a discriminant >= 0) + `round`; a trip in
+// which some lane records a leaf costs `push` more.  C = 1 at push = round = 0
+// is the loop as it is: its line must equal wave_cost's, digit for digit.
+struct DeferCost { double trips = 0, passes = 0, pass_lanes = 0, flushes = 0, roots = 0, valu = 0, visits = 0,
+                   tests = 0; size_t waves = 0, walks = 0; };
+struct DeferRay { V o, d; };
+static DeferCost defer_cost(const SphereBVH &b, const std::vector<float> &hot, const std::vector<DeferRay> &rays,
+                            int C, bool recull, bool join, const double c[5], double push, double round) {
+    DeferCost r;
+    struct Lane {
+        V o, d; double inv[3], ov[3]; uint32_t oct, node; Hit h;
+        int n; uint32_t leaf[8]; double tn[8];
+    };
+    for (size_t g = 0; g + 64 <= rays.size(); g += 64) {
+        Lane L[64];
+        ++r.waves;
+        r.walks += 64;
+        for (int l = 0; l < 64; ++l) {
+            Lane &x = L[l];
+            x.o = rays[g + l].o; x.d = rays[g + l].d; x.h = Hit{}; x.n = 0;
+            for (uint32_t i : b.big) {
+                const double t = sphere_t(x.o, x.d, &hot[(size_t)i * 4]);
+                if (t < x.h.t) { x.h.t = t; x.h.id = (int)i; }
+            }
+            x.inv[0] = 1 / x.d.x; x.inv[1] = 1 / x.d.y; x.inv[2] = 1 / x.d.z;
+            x.ov[0] = x.o.x; x.ov[1] = x.o.y; x.ov[2] = x.o.z;
+            x.oct = (x.inv[0] < 0 ? 1u : 0u) | (x.inv[1] < 0 ? 2u : 0u) | (x.inv[2] < 0 ? 4u : 0u);
+            x.node = 0;
+            if (b.nodes.size() > 8) {  // (the walk starts at the root's near child, as walk() with ev)
+                uint32_t a, ax;
+                std::memcpy(&a, &b.nodes[3], 4);
+                std::memcpy(&ax, &b.nodes[7], 4);
+                if (!(a & kLeafBit)) x.node = a + ((x.oct >> ax) & 1u);
+            }
+        }
+        // tests every taking-part lane's entries, pass by pass
+        auto flush = [&](const bool *part) {
+            ++r.flushes;
+            for (int k = 0; k < C; ++k) {
+                int lanes = 0, maxn = 0;
+                bool root_at[5] = {false, false, false, false, false};
+                for (int l = 0; l < 64; ++l) {
+                    Lane &x = L[l];
+                    if (!part[l] || k >= x.n) continue;
+                    if (recull && x.tn[k] > x.h.t) continue;
+                    ++lanes;
+                    uint32_t bb;
+                    std::memcpy(&bb, &b.nodes[(size_t)x.leaf[k] * 8 + 7], 4);
+                    uint32_t a;
+                    std::memcpy(&a, &b.nodes[(size_t)x.leaf[k] * 8 + 3], 4);
+                    const uint32_t first = a & ~kLeafBit;
+                    maxn = std::max(maxn, (int)std::min(bb, 5u));
+                    for (uint32_t j = first; j < first + bb; ++j) {
+                        const float *sp = &b.prims[(size_t)j * 4];
+                        const V oc = sub(x.o, V{sp[0], sp[1], sp[2]});
+                        const double hb = dot(oc, x.d);
+                        if (hb * hb - (dot(oc, oc) - sp[3]) >= 0 && j - first < 5) root_at[j - first] = true;
+                        const double t = sphere_t(x.o, x.d, sp);
+                        if (t < x.h.t) { x.h.t = t; x.h.id = (int)b.prim_id[j]; }
+                        ++r.tests;
+                    }
+                }
+                if (!lanes) continue;
+                ++r.passes;
+                r.pass_lanes += lanes;
+                int passes = 0;
+                for (int q = 0; q < maxn; ++q) passes += root_at[q] ? 1 : 0;
+                r.roots += passes;
+                r.valu += c[1] * maxn + c[2] * passes + round;
+            }
+            for (int l = 0; l < 64; ++l)
+                if (part[l]) L[l].n = 0;
+        };
+        for (;;) {
+            bool part[64];
+            int step = 0;
+            bool rec = false, full = false;
+            for (int l = 0; l < 64; ++l) {
+                Lane &x = L[l];
+                part[l] = join || x.node != kNodeEnd;  // (a lane that ends in this trip still takes part in its flush)
+                if (x.node == kNodeEnd) continue;
+                ++step;
+                ++r.visits;
+                const float *n = &b.nodes[(size_t)x.node * 8];
+                double tn = -INFINITY, tf = INFINITY;
+                for (int k = 0; k < 3; ++k) {
+                    const double t0 = (n[k] - x.ov[k]) * x.inv[k], t1 = (n[4 + k] - x.ov[k]) * x.inv[k];
+                    tn = std::max(tn, std::min(t0, t1));
+                    tf = std::min(tf, std::max(t0, t1));
+                }
+                uint32_t a, bb;
+                std::memcpy(&a, &n[3], 4);
+                std::memcpy(&bb, &n[7], 4);
+                const bool skip = tn > tf || tf < 1e-3 || tn > x.h.t;
+                const bool leaf = a & kLeafBit;
+                if (!skip && leaf) {
+                    x.leaf[x.n] = x.node; x.tn[x.n] = tn; ++x.n;
+                    rec = true;
+                    full = full || x.n >= C;
+                }
+                x.node = (skip || leaf) ? b.miss[(size_t)x.node * 8 + x.oct] : a + ((x.oct >> bb) & 1u);
+            }
+            if (!step) break;
+            ++r.trips;
+            r.valu += c[0];
+            if (rec) r.valu += push;
+            if (full) flush(part);
+        }
+        bool all[64], any = false;
+        for (int l = 0; l < 64; ++l) { all[l] = true; any = any || L[l].n; }
+        if (any) flush(all);
+    }
+    return r;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: sbvh_sim scene.txt [W H [S]]\n"); return 2; }
     std::ifstream f(argv[1]);
@@ -257,6 +383,7 @@ int main(int argc, char **argv) {
     const bool wave = std::getenv("SIM_WAVE") != nullptr;
     const int wave_bounce = std::getenv("SIM_WAVE_BOUNCE") ? std::atoi(std::getenv("SIM_WAVE_BOUNCE")) : 1;
     std::vector<std::vector<uint8_t>> events;  // SIM_WAVE: the recorded walks
+    std::vector<DeferRay> wave_rays;           // ... and their rays (SIM_WAVE_DEFER)
     for (int j = 0; j < H; ++j)
         for (int i = 0; i < W * S; ++i) {
             const int px = i / S;
@@ -275,6 +402,7 @@ int main(int argc, char **argv) {
                 }
                 const bool rec = wave && bounce == wave_bounce;
                 if (rec) events.emplace_back();
+                if (rec) wave_rays.push_back({o, d});
                 const int v2 = walk(b, hot, o, d, h, rec ? &events.back() : nullptr);
                 if (!bvh4) vis[bounce].push_back(v2);
                 if (h.id < 0) break;
@@ -313,6 +441,30 @@ int main(int argc, char **argv) {
             std::snprintf(name, sizeof name, "gated, T = %d", T);
             line(name, wave_cost(events, false, T, c), bv);
             if (gs) break;
+        }
+        // SIM_WAVE_DEFER=1: deferred leaf tests; SIM_DEFER_C (default: 1 2 3),
+        // SIM_DEFER_RECULL (default: both), SIM_DEFER_JOIN=1 (ended lanes take
+        // part in every flush), SIM_COST_PUSH / SIM_COST_ROUND (default 0)
+        if (std::getenv("SIM_WAVE_DEFER")) {
+            const double push = envd("SIM_COST_PUSH", 0), round = envd("SIM_COST_ROUND", 0);
+            const bool join = envd("SIM_DEFER_JOIN", 0) != 0;
+            const char *cs = std::getenv("SIM_DEFER_C"), *rs = std::getenv("SIM_DEFER_RECULL");
+            std::printf("deferred leaves (%s), push %.0f round %.0f\n",
+                        join ? "ended lanes join every flush" : "ended lanes keep their entries to the last flush",
+                        push, round);
+            for (int C : {1, 2, 3}) {
+                if (cs && std::atoi(cs) != C) continue;
+                for (int rc = 0; rc < 2; ++rc) {
+                    if ((rs && (std::atoi(rs) != 0) != (rc != 0)) || (C == 1 && rc)) continue;
+                    const DeferCost r = defer_cost(b, hot, wave_rays, C, rc != 0, join, c, push, round);
+                    const double n = r.waves ? (double)r.waves : 1.0, w = r.walks ? (double)r.walks : 1.0;
+                    std::printf("  C = %d%-8s trips %.1f, leaf passes %.2f with %.1f lanes, flushes %.2f, root passes %.2f, "
+                                "VALU %.0f per wave walk (%+.1f%%); per ray: %.2f node visits, %.2f sphere tests\n",
+                                C, rc ? " recull" : "", r.trips / n, r.passes / n,
+                                r.passes ? r.pass_lanes / r.passes : 0.0, r.flushes / n, r.roots / n, r.valu / n,
+                                bv > 0 ? 100.0 * (r.valu / n / bv - 1.0) : 0.0, r.visits / w, r.tests / w);
+                }
+            }
         }
     }
     for (int k = 0; k < 3; ++k) {
