@@ -82,7 +82,20 @@ __device__ __forceinline__ float xdiv(float a, float b, float y) {
 // enough for a >= 2^-96) pick it, as in the general sequence.  Inputs below
 // 2^-96 (and zero, negatives, NaN) take HIP's sqrtf.  Checked on the device
 // against sqrtf for all 2^32 inputs (tools/exactdiv_check.hip).
-__device__ __forceinline__ float xsqrt(float a) {
+//
+// Fallbacks, here and in xdivide3 / xunit3: the fast sequence runs in every
+// active lane without a branch (its value in a lane outside the guards is
+// never used), and one wave-wide test of the guard (a ballot, so a scalar
+// compare and one branch, no exec-mask save and restore) reaches the block
+// that computes HIP's result and selects it per lane.  Ordinary scenes never
+// enter that block; a wave that does pays for both sequences.
+// (the hint stands at the `if` itself: inside a helper it is lowered before
+// inlining, where it feeds a return and is lost, and the fallback block then
+// stays in the middle of the fast path, which jumps over it)
+#define XDIV_ANY_LANE(c) __builtin_expect(__builtin_amdgcn_ballot_w64(c) != 0ull, 0)
+
+// The unguarded sequence: RN(sqrt(a)) for a >= 2^-96.
+__device__ __forceinline__ float xsqrt_fast(float a) {
     const float s = __builtin_amdgcn_sqrtf(a);
     const float sm = __uint_as_float(__float_as_uint(s) - 1u);
     const float sp = __uint_as_float(__float_as_uint(s) + 1u);
@@ -90,8 +103,113 @@ __device__ __forceinline__ float xsqrt(float a) {
     const float rp = __builtin_fmaf(-sp, s, a);
     float r = rm <= 0.0f ? sm : s;
     r = rp > 0.0f ? sp : r;
-    if (__builtin_expect(!(a >= 0x1p-96f), 0)) r = __builtin_sqrtf(a);
     return r;
+}
+
+// kWaveGuard = false, here and below, is the per-lane form: the fallback in a
+// divergent region of its own (an exec-mask save and restore around it at
+// every site).  The triangle-mesh kernels keep it: they are at their register
+// limit, and holding the fast results across the wave-wide test cost two of
+// them scratch.
+template <bool kWaveGuard = true>
+__device__ __forceinline__ float xsqrt(float a) {
+    float r = xsqrt_fast(a);
+    const bool slow = !(a >= 0x1p-96f);
+    if (kWaveGuard) {
+        if (XDIV_ANY_LANE(slow)) {
+            // (an empty statement the compiler may not move or run ahead of the
+            // branch: without it the backend's if-conversion of wave-uniform
+            // branches computes sqrtf's expansion, 15 VALU, in every lane of every
+            // call and selects with s_cselect / v_cndmask instead of branching)
+            float t = a;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(t));
+#endif
+            r = slow ? __builtin_sqrtf(t) : r;
+        }
+    } else {
+        if (__builtin_expect(slow, 0)) r = __builtin_sqrtf(a);
+    }
+    return r;
+}
+
+// (x, y, z) / b, the bits of three `/`: one shared reciprocal and three
+// corrected quotients inside the guards, HIP's divide otherwise.
+template <bool kWaveGuard = true>
+__device__ __forceinline__ void xdivide3(float &x, float &y, float &z, float b) {
+    const bool ok = xdiv_den_ok(b) & xdiv_num3_ok(x, y, z);  // (bitwise: no branch)
+    if (!kWaveGuard) {
+        if (__builtin_expect(ok, 1)) {
+            const float r = xdiv_rcp(b);
+            x = xdiv(x, b, r);
+            y = xdiv(y, b, r);
+            z = xdiv(z, b, r);
+        } else {
+            x = x / b;
+            y = y / b;
+            z = z / b;
+        }
+        return;
+    }
+    const float r = xdiv_rcp(b);
+    float qx = xdiv(x, b, r), qy = xdiv(y, b, r), qz = xdiv(z, b, r);
+    if (XDIV_ANY_LANE(!ok)) {
+        const float sx = x / b, sy = y / b, sz = z / b;
+        qx = ok ? qx : sx;
+        qy = ok ? qy : sy;
+        qz = ok ? qz : sz;
+    }
+    x = qx;
+    y = qy;
+    z = qz;
+}
+
+// NVec3::new (maths.rs:111-118): (x, y, z) / sqrt((x*x + y*y) + z*z).  The
+// components are bounded by the length, so the cheaper numerator guard does.
+//
+// One guard for the root and the quotients.  The length is the unguarded
+// root; when it fails xdiv_den_ok (outside [2^-40, 2^40], or NaN) or a
+// component fails its guard, the fallback block takes the length from sqrtf
+// and divides with `/`, so nothing of the fast sequence is used.  When the
+// fast root len passes, len >= 2^-40, and v_sqrt_f32 being within one ulp and
+// the residual step moving it by at most one more puts the exact root above
+// 2^-40 (1 - 2^-22), so the sum is >= 2^-81 > 2^-96, where xsqrt_fast is the
+// exact root: xsqrt's own guard could not have fired.  That covers normal
+// inputs; that no zero, denormal, negative or NaN sum yields a fast root
+// inside [2^-40, 2^40] is checked with every other input: for all 2^32 sums
+// `den_ok(fast) ? fast : sqrtf` has the bits of sqrtf (tools/exactdiv_check.hip).
+template <bool kWaveGuard = true>
+__device__ __forceinline__ void xunit3(float &x, float &y, float &z) {
+#pragma clang fp contract(off)
+    const float n = (x * x + y * y) + z * z;
+    if (!kWaveGuard) {  // (the root with its own guard, then the quotients')
+        const float len = xsqrt<false>(n);
+        if (__builtin_expect(xdiv_den_ok(len) & xdiv_num3_small_ok(x, y, z), 1)) {
+            const float r = xdiv_rcp(len);
+            x = xdiv(x, len, r);
+            y = xdiv(y, len, r);
+            z = xdiv(z, len, r);
+        } else {
+            x = x / len;
+            y = y / len;
+            z = z / len;
+        }
+        return;
+    }
+    const float len = xsqrt_fast(n);
+    const bool ok = xdiv_den_ok(len) & xdiv_num3_small_ok(x, y, z);
+    const float r = xdiv_rcp(len);
+    float qx = xdiv(x, len, r), qy = xdiv(y, len, r), qz = xdiv(z, len, r);
+    if (XDIV_ANY_LANE(!ok)) {
+        const float slen = __builtin_sqrtf(n);
+        const float sx = x / slen, sy = y / slen, sz = z / slen;
+        qx = ok ? qx : sx;
+        qy = ok ? qy : sy;
+        qz = ok ? qz : sz;
+    }
+    x = qx;
+    y = qy;
+    z = qz;
 }
 
 }  // namespace rtamd

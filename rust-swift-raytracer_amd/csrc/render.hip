@@ -56,28 +56,28 @@ __device__ __forceinline__ F3 cross(F3 a, F3 b) {  // maths.rs:88-94
 // The divisions go through exactdiv.h (one shared correctly rounded
 // reciprocal, three corrected quotients: the same bits as `/`) whenever the
 // operands are in its guarded range; HIP's divide otherwise (never taken by
-// lanes of ordinary scenes, so the branch is skipped wave-wide).
+// lanes of ordinary scenes: one wave-wide test skips it, see exactdiv.h).
 // RT_NO_XDIV builds the plain-divide variant (A/B only).
+// kWaveGuard (exactdiv.h): true in every kernel but the triangle-mesh ones
+// (kMesh >= 2), which keep the per-lane fallbacks.
+template <bool kWaveGuard>
 __device__ __forceinline__ F3 divide_by(F3 a, float b) {
 #ifndef RT_NO_XDIV
-    // (bitwise: both guards evaluate without a branch)
-    if (__builtin_expect((unsigned)xdiv_den_ok(b) & (unsigned)xdiv_num3_ok(a.x, a.y, a.z), 1)) {
-        const float y = xdiv_rcp(b);
-        return F3{xdiv(a.x, b, y), xdiv(a.y, b, y), xdiv(a.z, b, y)};
-    }
-#endif
+    xdivide3<kWaveGuard>(a.x, a.y, a.z, b);
+    return a;
+#else
     return F3{a.x / b, a.y / b, a.z / b};
-}
-__device__ __forceinline__ F3 unit(F3 a) {  // NVec3::new, maths.rs:111-118
-    const float len = xsqrt((a.x * a.x + a.y * a.y) + a.z * a.z);
-#ifndef RT_NO_XDIV
-    // components are bounded by the length: the cheaper numerator guard
-    if (__builtin_expect((unsigned)xdiv_den_ok(len) & (unsigned)xdiv_num3_small_ok(a.x, a.y, a.z), 1)) {
-        const float y = xdiv_rcp(len);
-        return F3{xdiv(a.x, len, y), xdiv(a.y, len, y), xdiv(a.z, len, y)};
-    }
 #endif
+}
+template <bool kWaveGuard>
+__device__ __forceinline__ F3 unit(F3 a) {  // NVec3::new, maths.rs:111-118
+#ifndef RT_NO_XDIV
+    xunit3<kWaveGuard>(a.x, a.y, a.z);
+    return a;
+#else
+    const float len = xsqrt<kWaveGuard>((a.x * a.x + a.y * a.y) + a.z * a.z);
     return F3{a.x / len, a.y / len, a.z / len};
+#endif
 }
 
 // xorshift32 (random.rs:22-30); `x as f32 / u32::MAX as f32` == RN(x) * 2^-32.
@@ -101,11 +101,12 @@ __device__ __forceinline__ float draw_plus(uint32_t &s, float n) {
     return __builtin_fmaf((float)xorshift(s), 0x1p-32f, n);
 }
 // common.rs:32-38 -- three draws x, y, z, normalised (no rejection sampling).
+template <bool kWaveGuard>
 __device__ __forceinline__ F3 draw_unit(uint32_t &s) {
     float x = draw11(s);
     float y = draw11(s);
     float z = draw11(s);
-    return unit(F3{x, y, z});
+    return unit<kWaveGuard>(F3{x, y, z});
 }
 
 __device__ __forceinline__ uint32_t counter_seed(uint32_t seed, uint64_t job) {
@@ -173,6 +174,7 @@ constexpr uint32_t kBatch = 8;  // spheres per scalar-load batch (sphere count p
 // The last batch tests only the scene's spheres: a wave-uniform guard skips
 // the padding's arithmetic (world.txt's 9 spheres took 16 tests per ray;
 // RT_BRUTE_PADDED restores the padded batches).
+template <bool kWaveGuard>
 __device__ __forceinline__ void spheres_brute(const TraceParams &p, F3 org, F3 dir, float &best_t,
                                               int &best_i) {
     const float tmin = 0.001f;
@@ -201,7 +203,7 @@ __device__ __forceinline__ void spheres_brute(const TraceParams &p, F3 org, F3 d
 #pragma unroll
         for (uint32_t k = 0; k < kBatch; ++k) {
             if (disc[k] >= 0.0f) {
-                const float sq = xsqrt(disc[k]);
+                const float sq = xsqrt<kWaveGuard>(disc[k]);
                 const float r1 = -hb[k] - sq;
                 const float r2 = -hb[k] + sq;
                 const bool ok1 = (tmin < r1) && (r1 < best_t);
@@ -218,6 +220,7 @@ __device__ __forceinline__ void spheres_brute(const TraceParams &p, F3 org, F3 d
 // One sphere in any order: same arithmetic as Sphere::hit (common.rs:74-92);
 // the candidate (root1 if > t_min, else root2 if > t_min) is independent of
 // t_max, and the reference keeps the smallest candidate, lowest index first.
+template <bool kWaveGuard>
 __device__ __forceinline__ bool sphere_candidate(float4 S, F3 org, F3 dir, int idx, float &best_t,
                                                  int &best_i) {
     const float tmin = 0.001f;
@@ -226,7 +229,7 @@ __device__ __forceinline__ bool sphere_candidate(float4 S, F3 org, F3 dir, int i
     const float cc = ((ocx * ocx + ocy * ocy) + ocz * ocz) - S.w;
     const float disc = hb * hb - cc;
     if (!(disc >= 0.0f)) return false;
-    const float sq = xsqrt(disc);
+    const float sq = xsqrt<kWaveGuard>(disc);
     const float r1 = -hb - sq;
     const float r2 = -hb + sq;
     const bool v1 = tmin < r1;
@@ -239,6 +242,9 @@ __device__ __forceinline__ bool sphere_candidate(float4 S, F3 org, F3 dir, int i
     // never takes, is excluded
     const uint64_t kc = ((uint64_t)__float_as_uint(c) << 32) | (uint32_t)idx;
     const uint64_t kb = ((uint64_t)__float_as_uint(best_t) << 32) | (uint32_t)best_i;
+    // (a block of its own around the compare and the two moves: folding it into
+    // the select mask of two v_cndmask measured 0.016 ms slower on C2 and 0.19 ms
+    // on C3)
     const bool take = valid && c != __builtin_inff() && kc < kb;
     if (take) { best_t = c; best_i = idx; }
     return take;
@@ -288,13 +294,14 @@ __device__ __forceinline__ float sph_inflation(const TraceParams &p, SphBound b,
     return fminf(kErrK * s, (kErrKq * s) * (s * p.bvh_inv_rmin)) + b.e_abs;
 }
 
+template <bool kWaveGuard>
 __device__ __forceinline__ void spheres_big(const TraceParams &p, F3 org, F3 dir, float &best_t,
                                             int &best_i) {
     for (uint32_t k = 0; k < p.nbig; ++k) {
         // (both scalar loads: a vector load here made the ray setup wait on
         // every outstanding vector memory op, vmcnt(0))
         const float4 S = uniform_load(p.big_hot, k);
-        sphere_candidate(S, org, dir, (int)uniform_load_u32(p.big_id, k), best_t, best_i);
+        sphere_candidate<kWaveGuard>(S, org, dir, (int)uniform_load_u32(p.big_id, k), best_t, best_i);
     }
 }
 
@@ -492,7 +499,7 @@ __device__ __forceinline__ void sphere_slabs(F3 org, F3 inv, float e, F3 &nlo, F
 // with the first one's, before the first test, so a two-sphere leaf waits for
 // the LDS once; a one-sphere leaf's read of entry first + 1 stays inside the
 // workgroup's LDS image (the id words follow the records) and is not used.
-template <bool kAhead = false>
+template <bool kWaveGuard, bool kAhead = false>
 __device__ __forceinline__ void sphere_leaf(const BvhView &v, F3 org, F3 dir, uint32_t leaf, float &best_t,
                                             int &best_i, uint32_t &sph_tests) {
     const uint32_t first = leaf >> 3, n = leaf & 7u;
@@ -506,20 +513,20 @@ __device__ __forceinline__ void sphere_leaf(const BvhView &v, F3 org, F3 dir, ui
         S1 = v.prims[first + 1];
         i1 = (int)v.ids[first + 1];
     }
-    sphere_candidate(v.prims[first], org, dir, (int)v.ids[first], best_t, best_i);
+    sphere_candidate<kWaveGuard>(v.prims[first], org, dir, (int)v.ids[first], best_t, best_i);
     if (n > 1u) {
         if (!kAhead) {
             S1 = v.prims[first + 1];
             i1 = (int)v.ids[first + 1];
         }
-        sphere_candidate(S1, org, dir, i1, best_t, best_i);
+        sphere_candidate<kWaveGuard>(S1, org, dir, i1, best_t, best_i);
         for (uint32_t j = first + 2; j < first + n; ++j)
-            sphere_candidate(v.prims[j], org, dir, (int)v.ids[j], best_t, best_i);
+            sphere_candidate<kWaveGuard>(v.prims[j], org, dir, (int)v.ids[j], best_t, best_i);
     }
 #else
     for (uint32_t j = first; j < first + n; ++j) {
         ++sph_tests;
-        sphere_candidate(v.prims[j], org, dir, (int)v.ids[j], best_t, best_i);
+        sphere_candidate<kWaveGuard>(v.prims[j], org, dir, (int)v.ids[j], best_t, best_i);
     }
 #endif
 }
@@ -1265,6 +1272,7 @@ template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial
 __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, AccumTail tail = AccumTail{},
                                            AdaptTail xtail_arg = AdaptTail{}) {
     static_assert(!(kAccum && kAdapt), "an adaptive pass is an instance of its own");
+    constexpr bool kWaveGuard = kMesh < 2;  // (exactdiv.h; the mesh kernels keep the per-lane fallbacks)
 #ifndef RT_COUNT_DEFER  // (diagnostic build: the counting corner instance with the deferred walk)
     static_assert(kDefer == 0 || (kCorner && !kCount && !kStep && !kSerial && kMesh == 0),
                   "deferred leaves: the lean whole-walk corner kernel");
@@ -1491,7 +1499,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     best_t = __builtin_inff();
                     best_i = -1;
                     if (kBvh) {
-                        spheres_big(p, org, dir, best_t, best_i);
+                        spheres_big<kWaveGuard>(p, org, dir, best_t, best_i);
                         if (!kWalkState)
                             node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
                                            : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
@@ -1503,16 +1511,16 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                             // arithmetic and (t, index) argmin as sphere_leaf)
                             const uint32_t nc = spl1 >> 16;
                             sph_tests += nc;
-                            if (nc > 0) sphere_candidate(view.prims[spl0 & 0xFFFFu], org, dir,
+                            if (nc > 0) sphere_candidate<kWaveGuard>(view.prims[spl0 & 0xFFFFu], org, dir,
                                                          (int)view.ids[spl0 & 0xFFFFu], best_t, best_i);
-                            if (nc > 1) sphere_candidate(view.prims[spl0 >> 16], org, dir,
+                            if (nc > 1) sphere_candidate<kWaveGuard>(view.prims[spl0 >> 16], org, dir,
                                                          (int)view.ids[spl0 >> 16], best_t, best_i);
-                            if (nc > 2) sphere_candidate(view.prims[spl1 & 0xFFFFu], org, dir,
+                            if (nc > 2) sphere_candidate<kWaveGuard>(view.prims[spl1 & 0xFFFFu], org, dir,
                                                          (int)view.ids[spl1 & 0xFFFFu], best_t, best_i);
                             phase = kTriInit;
                         }
                     } else {
-                        spheres_brute(p, org, dir, best_t, best_i);
+                        spheres_brute<kWaveGuard>(p, org, dir, best_t, best_i);
                         phase = kTriInit;
                     }
                 }
@@ -1575,7 +1583,8 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                                 const uint32_t ent = (uint32_t)(pend >> 16 * r) & 0xFFFFu;
                                 if (ent != 0u &&
                                     !(kLeafRecull && __float_as_int(tnr[r]) > __float_as_int(best_t)))
-                                    sphere_leaf<true>(view, org, dir, ent & 0x7FFFu, best_t, best_i, sph_tests);
+                                    sphere_leaf<kWaveGuard, true>(view, org, dir, ent & 0x7FFFu, best_t, best_i,
+                                                             sph_tests);
                             }
                             pend = 0;
                         };
@@ -1605,7 +1614,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     do {
                         uint32_t leaf;
                         if (sphere_node_corner(offn, offf, inv, best_t, nn, nf, node, leaf, node_tests))
-                            sphere_leaf<true>(view, org, dir, leaf, best_t, best_i, sph_tests);
+                            sphere_leaf<kWaveGuard, true>(view, org, dir, leaf, best_t, best_i, sph_tests);
                     } while (node != 0xFFFFu && (!kStep || --budget != 0));
                 } else {
                     F3 nlo, nhi;
@@ -1626,7 +1635,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                             wt += any2 ? 2u : any1 ? 1u : 0u;
                         }
 #endif
-                        if (lf) sphere_leaf<kLds>(view, org, dir, leaf, best_t, best_i, sph_tests);
+                        if (lf) sphere_leaf<kWaveGuard, kLds>(view, org, dir, leaf, best_t, best_i, sph_tests);
                     } while (node != kEnd && (!kStep || --budget != 0));
 #ifdef RT_WALK_MIX
                     if (kCount) {
@@ -1829,9 +1838,9 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     SM = view.shade[2 * best_i + 1];
                     skind = view.kinds[best_i];
                     spos = org + scale(dir, best_t);
-                    un = divide_by(spos - f3(SS.x, SS.y, SS.z), SS.w);
+                    un = divide_by<kWaveGuard>(spos - f3(SS.x, SS.y, SS.z), SS.w);
                 }
-                if (sky || sph) un = unit(un);
+                if (sky || sph) un = unit<kWaveGuard>(un);
                 if (sky) {
                     // background (common.rs:276-281): re-normalise, lerp to sky blue
                     const float t = 0.5f * (un.y + 1.0f);
@@ -1865,7 +1874,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     bool next = true, keep_normal = false;
                     F3 v = nrm;
                     if (kind == kMatDiffuse || kind == kMatMetal) {
-                        const F3 ru = draw_unit(rng);
+                        const F3 ru = draw_unit<kWaveGuard>(rng);
                         if (kSerial) ++nscat;
                         if (kind == kMatDiffuse) {  // materials.rs:42-52
                             v = nrm + ru;
@@ -1882,7 +1891,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                         if (dot(dir, nrm) >= 0.0f) { n2 = -nrm; eta = 1.0f / param; }
                         const float cos_t = dot(-dir, n2);  // maths.rs:31-36
                         const F3 perp = scale(dir + scale(n2, cos_t), eta);
-                        const F3 par = scale(n2, -xsqrt(fabsf(1.0f - dot(perp, perp))));
+                        const F3 par = scale(n2, -xsqrt<kWaveGuard>(fabsf(1.0f - dot(perp, perp))));
                         v = perp + par;
                         cr = cg = cb = 1.0f;
                     } else {  // Emission (materials.rs:100-102)
@@ -2158,7 +2167,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
             }
         }
         RT_STAMP(6);
-        if (renorm) dir = unit(vdir);
+        if (renorm) dir = unit<kWaveGuard>(vdir);
         RT_STAMP(0);
         if (__ballot(active) == 0 && exhausted) break;
     }
@@ -2508,6 +2517,7 @@ hipError_t launch_resolve_ex(const float *samples, uint32_t *out, uint32_t npix,
 template <bool kBvh, bool kLds, int kMesh>
 __device__ __forceinline__ uint32_t serial_trace_b(const TraceParams &p, const BvhView &view, uint32_t sph_root,
                                                 uint32_t rng, uint32_t j) {
+    constexpr bool kWaveGuard = kMesh < 2;  // (as in trace_body)
     const uint32_t pix = fdiv(j, p.div_sspp);
     const uint32_t row = fdiv(pix, p.div_width);
     const uint32_t col = pix - row * p.width;
@@ -2524,7 +2534,7 @@ __device__ __forceinline__ uint32_t serial_trace_b(const TraceParams &p, const B
     const F3 vv = f3(p.cam[9], p.cam[10], p.cam[11]);
     F3 org = f3(p.cam[0], p.cam[1], p.cam[2]);
     const F3 llc = f3(p.cam[3], p.cam[4], p.cam[5]);
-    F3 dir = unit(((llc + scale(h, u)) + scale(vv, v)) - org);
+    F3 dir = unit<kWaveGuard>(((llc + scale(h, u)) + scale(vv, v)) - org);
     uint32_t b = 0, cnt = 0;  // (cnt: the helpers' work counters, unused)
     for (int32_t bounce = 0; bounce < p.depth; ++bounce) {
         const F3 inv = f3(slab_rcp(dir.x), slab_rcp(dir.y), slab_rcp(dir.z));
@@ -2532,7 +2542,7 @@ __device__ __forceinline__ uint32_t serial_trace_b(const TraceParams &p, const B
         float best_t = __builtin_inff();
         int best_i = -1;
         if (kBvh) {  // World::hit (common.rs:241-247) through the exact tree
-            spheres_big(p, org, dir, best_t, best_i);
+            spheres_big<kWaveGuard>(p, org, dir, best_t, best_i);
             constexpr uint32_t kEnd = kLds ? 0xFFFFu : kNodeEndDev;
             const SphBound bnd = sph_bound(p, org);
             F3 nlo, nhi;
@@ -2542,10 +2552,10 @@ __device__ __forceinline__ uint32_t serial_trace_b(const TraceParams &p, const B
             do {
                 uint32_t leaf;
                 if (sphere_node<kLds>(view, inv, ooff, best_t, nlo, nhi, node, leaf, cnt))
-                    sphere_leaf(view, org, dir, leaf, best_t, best_i, cnt);
+                    sphere_leaf<kWaveGuard>(view, org, dir, leaf, best_t, best_i, cnt);
             } while (node != kEnd);
         } else {
-            spheres_brute(p, org, dir, best_t, best_i);
+            spheres_brute<kWaveGuard>(p, org, dir, best_t, best_i);
         }
         float tri_t = __builtin_inff();  // Mesh::hit (common.rs:178-223)
         int tri_i = -1;
@@ -2586,12 +2596,12 @@ __device__ __forceinline__ uint32_t serial_trace_b(const TraceParams &p, const B
             param = view.shade[2 * best_i + 1].w;
             kind = view.kinds[best_i];
             pos = org + scale(dir, best_t);
-            nrm = unit(divide_by(pos - f3(S.x, S.y, S.z), S.w));  // common.rs:95
+            nrm = unit<kWaveGuard>(divide_by<kWaveGuard>(pos - f3(S.x, S.y, S.z), S.w));  // common.rs:95
         }
         F3 v = nrm;
         bool keep_normal = false;
         if (kind == kMatDiffuse || kind == kMatMetal) {
-            const F3 ru = draw_unit(rng);
+            const F3 ru = draw_unit<kWaveGuard>(rng);
             ++b;
             if (kind == kMatDiffuse) {  // materials.rs:42-52
                 v = nrm + ru;
@@ -2608,13 +2618,13 @@ __device__ __forceinline__ uint32_t serial_trace_b(const TraceParams &p, const B
             if (dot(dir, nrm) >= 0.0f) { n2 = -nrm; eta = 1.0f / param; }
             const float cos_t = dot(-dir, n2);
             const F3 perp = scale(dir + scale(n2, cos_t), eta);
-            const F3 par = scale(n2, -xsqrt(fabsf(1.0f - dot(perp, perp))));
+            const F3 par = scale(n2, -xsqrt<kWaveGuard>(fabsf(1.0f - dot(perp, perp))));
             v = perp + par;
         } else {
             return b;  // Emission (materials.rs:100-102)
         }
         org = pos;
-        dir = keep_normal ? nrm : unit(v);
+        dir = keep_normal ? nrm : unit<kWaveGuard>(v);
     }
     return b;  // depth exhausted (common.rs:284)
 }

@@ -7,6 +7,9 @@
 //   3. Numerator edge values (+-0, +-2^-60, +-(2^60 - ulp)) against every
 //      denominator of (2); the guard predicates on boundary values.
 //   4. xsqrt(a) == sqrtf(a) for all 2^32 inputs.
+//   5. xunit3's single guard: for all 2^32 sums a, the unguarded root when it
+//      passes xdiv_den_ok and sqrtf otherwise has the bits of sqrtf(a).
+//      (`exactdiv_check root` runs this check alone.)
 // Prints the mismatch counts and exits 1 on any mismatch.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I../rust-swift-raytracer_amd/csrc
 #include <hip/hip_runtime.h>
@@ -14,6 +17,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "exactdiv.h"
@@ -105,6 +109,32 @@ __global__ void sqrt_kernel(Bad *bad) {
     }
 }
 
+// xunit3's rule for its length: the fast root if it passes the denominator
+// guard, else the fallback block's sqrtf
+__global__ void root_kernel(Bad *bad) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (1ull << 32);
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t bits = (uint32_t)i;
+        const float a = __uint_as_float(bits);
+        const float ref = __builtin_sqrtf(a);
+        const float fast = xsqrt_fast(a);
+        const float len = xdiv_den_ok(fast) ? fast : ref;
+        if (__float_as_uint(len) != __float_as_uint(ref)) record(bad, bits, 0);
+    }
+}
+
+static bool check_root() {
+    Bad *rt;
+    CHECK(hipMallocManaged(&rt, sizeof(Bad)));
+    *rt = Bad{0, 0, 0};
+    hipLaunchKernelGGL(root_kernel, dim3(16384), dim3(256), 0, 0, rt);
+    CHECK(hipDeviceSynchronize());
+    printf("unit root: all 2^32 sums, %llu mismatches", rt->count);
+    if (rt->count) printf(" (first a=0x%08x)", rt->first_a);
+    printf("\n");
+    return rt->count == 0;
+}
+
 static uint32_t xs32(uint32_t &s) {
     s ^= s << 13;
     s ^= s >> 17;
@@ -113,6 +143,11 @@ static uint32_t xs32(uint32_t &s) {
 }
 
 int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "root") {
+        const bool ok = check_root();
+        printf("%s\n", ok ? "exactdiv root OK" : "exactdiv root FAILED");
+        return ok ? 0 : 1;
+    }
     const uint32_t nden = argc > 1 ? (uint32_t)atoi(argv[1]) : 4096u;
     Bad *bad;
     CHECK(hipMallocManaged(&bad, 3 * sizeof(Bad)));
@@ -171,7 +206,9 @@ int main(int argc, char **argv) {
     printf("sqrt: all 2^32 inputs, %llu mismatches", sq->count);
     if (sq->count) printf(" (first a=0x%08x)", sq->first_a);
     printf("\n");
-    const bool ok = bad[0].count == 0 && bad[1].count == 0 && bad[2].count == 0 && sq->count == 0;
+    // 5. the length rule of xunit3
+    const bool root_ok = check_root();
+    const bool ok = bad[0].count == 0 && bad[1].count == 0 && bad[2].count == 0 && sq->count == 0 && root_ok;
     printf("%s\n", ok ? "exactdiv OK" : "exactdiv FAILED");
     return ok ? 0 : 1;
 }
