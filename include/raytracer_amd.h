@@ -356,6 +356,59 @@ int rt_world_set_sphere_material(Rust_WorldHandle *handle, size_t i, const float
 int rt_world_set_triangle_material(Rust_WorldHandle *handle, size_t i, const float material[6]);
 /* origin, lower_left_corner, horizontal, vertical (camera.rs:8-15) */
 void rt_camera_get(const Rust_Camera *camera, float out[12]);
+
+/* Cameras beyond the scene file's `camera origin ... aspect ...;` (always
+ * looking down -z): the reference crate's other two constructors, which its
+ * C-ABI never exported.  Each returns a camera that no handle owns; the caller
+ * swaps it in:
+ *
+ *   Rust_Camera *c = rt_camera_new_look_at(from, to, up, fov, aspect);
+ *   if (c) { rt_camera_free(handle->camera); handle->camera = c; }
+ *
+ * The field of view is in radians (camera.rs:5 Radians).  Every step is one
+ * f32 operation in the reference's order (camera.rs:34-69, maths.rs:88-137,
+ * 204-214): `up` is normalised first (NVec3::new), u = up x w and v = w x u
+ * are NOT renormalised, and tan is the host libm's tanf, as Rust's f32::tan
+ * is the platform's.  So the 12 floats are the reference's on the same host.
+ *
+ * Deviation: where the reference asserts (origin - look_at near zero, i.e.
+ * every |component| < 1e-8; |v.y| > 1e-8 false, NaN included) rt_camera_new_
+ * look_at returns NULL with rt_last_error set, like load_world on a parse
+ * error.  rt_camera_from_floats rejects nothing: it is the inverse of
+ * rt_camera_get on bits (a mirrored or singular camera renders; it only loses
+ * the primary candidate lists where they do not apply).
+ *
+ * Every frame, accumulator pass and multi-device frame takes the handle's
+ * camera as its 12 floats; accumulators reset when any of them changes, so a
+ * mouse-look loop is "rt_camera_new_look_at, swap, add, show". */
+Rust_Camera *rt_camera_new_with_vertical_fov(const float origin[3], float vertical_fov,
+                                             float aspect_ratio);
+Rust_Camera *rt_camera_new_look_at(const float origin[3], const float look_at[3],
+                                   const float up[3], float vertical_fov, float aspect_ratio);
+Rust_Camera *rt_camera_from_floats(const float camera[12]);
+/* Consumes `camera` like move_camera_position and returns it moved: origin
+ * and lower_left_corner + (x, y, z), one f32 add per component; horizontal
+ * and vertical (the orientation and the field of view) stay.
+ * move_camera_position itself remains the reference's
+ * Camera::new_at(position + d, horizontal.x / vertical.y) (lib.rs:60-63),
+ * which drops an oriented camera's orientation. */
+Rust_Camera *rt_camera_translate(Rust_Camera *camera, float x, float y, float z);
+/* Frees a camera that no handle owns (NULL is fine). */
+void rt_camera_free(Rust_Camera *camera);
+
+/* Diagnostics: where the primary triangle strip lists of the LAST frame trace
+ * launch on `device` (-1 = current) were built.  0: the launch used none,
+ * 1: on the host (bvh.h build_primary_tri_lists, then uploaded), 2: on the
+ * device, on the frame's stream (RT_AMD_GPU_TRI_LISTS=0 keeps
+ * the host build).  Both hold the same bytes.  Negative: an error. */
+int rt_primary_tri_lists(const Rust_WorldHandle *handle, int device);
+/* Diagnostics: how often the camera-origin triangle records of this world
+ * were built (load_world builds them once for the scene's camera; 0 for a
+ * scene without a triangle tree).  They are keyed on the camera origin alone:
+ * a camera that turns or zooms in place leaves the count alone, and only the
+ * primary lists are rebuilt.  Negative: an error. */
+long rt_camera_record_builds(const Rust_WorldHandle *handle);
+
 /* ParseError discriminant of the last failed load_world (parser.rs:11-18),
  * 100 = input on which the reference panics, -1 = none. */
 int rt_last_parse_error(void);

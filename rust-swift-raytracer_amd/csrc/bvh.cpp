@@ -1001,7 +1001,11 @@ static bool camera_inverse(const CameraModel &cam, double Mi[3][3]) {
     const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) -
                        M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
                        M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return false;
+    // Every camera the constructors make has det < 0 (h, v, -w right-handed,
+    // camera.rs:56-66), and that is what the lists' margins were checked on: a
+    // mirrored (det > 0) or singular camera from rt_camera_from_floats renders
+    // without lists
+    if (!(det < 0) || !std::isfinite(det)) return false;
     Mi[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) / det;
     Mi[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det;
     Mi[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) / det;
@@ -1112,6 +1116,27 @@ PrimarySphereLists build_primary_sphere_lists(const SphereBVH &bv, const CameraM
     return out;
 }
 
+bool tri_list_params(const CameraTriangleBVH &ct, const CameraModel &cam, size_t width, size_t height,
+                     TriListParams &out) {
+    // (the checks and constants of build_primary_tri_lists below; camera_inverse
+    // holds the same expressions as its adjugate)
+    const size_t n = ct.rec_box.size() / 6;
+    if (n == 0 || n > 0x7FFFFFFFu || width < 2 || height < 2 || height > (1u << 24) || width > (1u << 24))
+        return false;
+    double Mi[3][3];
+    if (!camera_inverse(cam, Mi)) return false;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) out.Mi[3 * r + c] = Mi[r][c];
+    out.o[0] = cam.origin.x; out.o[1] = cam.origin.y; out.o[2] = cam.origin.z;
+    out.wden = (double)(float)(width - 1);
+    out.hden = (double)(float)(height - 1);
+    out.n = (uint32_t)n;
+    out.width = (uint32_t)width;
+    out.height = (uint32_t)height;
+    out.strips_per_row = (uint32_t)((width + kTriStripW - 1) / kTriStripW);
+    return true;
+}
+
 PrimaryTriLists build_primary_tri_lists(const CameraTriangleBVH &ct, const CameraModel &cam,
                                         size_t width, size_t height) {
     PrimaryTriLists out;
@@ -1127,7 +1152,7 @@ PrimaryTriLists build_primary_tri_lists(const CameraTriangleBVH &ct, const Camer
     const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) -
                        M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
                        M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return out;
+    if (!(det < 0) || !std::isfinite(det)) return out;  // (camera_inverse: no lists for det >= 0)
     double Mi[3][3];  // inverse via the adjugate
     Mi[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) / det;
     Mi[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det;

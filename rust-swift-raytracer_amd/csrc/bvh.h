@@ -189,6 +189,17 @@ struct PrimaryTriLists {
 PrimaryTriLists build_primary_tri_lists(const CameraTriangleBVH &ct, const CameraModel &cam,
                                         size_t width, size_t height);
 
+// The same build on the device (tri_lists.hip): the host's checks and the
+// per-frame constants; false = no lists (build_primary_tri_lists returns none).
+struct TriListParams {
+    double Mi[9];          // inverse camera map, row-major
+    double o[3];           // camera origin
+    double wden, hden;
+    uint32_t n, width, height, strips_per_row;
+};
+bool tri_list_params(const CameraTriangleBVH &ct, const CameraModel &cam, size_t width, size_t height,
+                     TriListParams &out);
+
 // Primary-ray sphere candidates (bounce 0, instead of the sphere-tree walk).
 // A primary ray of pixel (col, row) points into that pixel's footprint, so
 // only tree spheres whose inflated ball (radius r + K(|o - c| + r) + e_abs, the

@@ -296,6 +296,71 @@ void rt_camera_get(const Rust_Camera *c, float out[12]) {
     for (int k = 0; k < 4; ++k) { out[3 * k] = v[k].x; out[3 * k + 1] = v[k].y; out[3 * k + 2] = v[k].z; }
 }
 
+// ---- cameras no handle owns yet (camera.rs:34-69); the caller swaps one in:
+// rt_camera_free(h->camera); h->camera = c;
+Rust_Camera *rt_camera_new_with_vertical_fov(const float origin[3], float vertical_fov, float aspect_ratio) {
+    if (!origin) {
+        rtamd::set_error("rt_camera_new_with_vertical_fov: null origin");
+        return nullptr;
+    }
+    return new Rust_Camera{rtamd::camera_with_vertical_fov({origin[0], origin[1], origin[2]}, vertical_fov,
+                                                           aspect_ratio)};
+}
+
+Rust_Camera *rt_camera_new_look_at(const float origin[3], const float look_at[3], const float up[3],
+                                   float vertical_fov, float aspect_ratio) {
+    if (!origin || !look_at || !up) {
+        rtamd::set_error("rt_camera_new_look_at: null argument");
+        return nullptr;
+    }
+    rtamd::CameraModel cam;
+    const int rc = rtamd::camera_look_at({origin[0], origin[1], origin[2]}, {look_at[0], look_at[1], look_at[2]},
+                                         {up[0], up[1], up[2]}, vertical_fov, aspect_ratio, cam);
+    if (rc != 0) {  // (the reference asserts, camera.rs:50 and :61)
+        rtamd::set_error(rc == 1 ? "rt_camera_new_look_at: origin and look_at must differ"
+                                 : "rt_camera_new_look_at: the view's vertical has no y component "
+                                   "(up along the view direction, or a NaN)");
+        return nullptr;
+    }
+    return new Rust_Camera{cam};
+}
+
+Rust_Camera *rt_camera_from_floats(const float camera[12]) {
+    if (!camera) {
+        rtamd::set_error("rt_camera_from_floats: null camera");
+        return nullptr;
+    }
+    static_assert(sizeof(rtamd::CameraModel) == 12 * sizeof(float), "CameraModel is rt_camera_get's 12 floats");
+    auto *c = new Rust_Camera{};
+    std::memcpy(&c->cam, camera, 12 * sizeof(float));  // (bits as given, NaN payloads included)
+    return c;
+}
+
+Rust_Camera *rt_camera_translate(Rust_Camera *camera, float x, float y, float z) {
+    if (!camera) return nullptr;
+    camera->cam = rtamd::camera_translated(camera->cam, x, y, z);
+    return camera;
+}
+
+void rt_camera_free(Rust_Camera *camera) { delete camera; }
+
+int rt_primary_tri_lists(const Rust_WorldHandle *h, int device) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_primary_tri_lists: null argument");
+        return -1;
+    }
+    return rtamd::primary_tri_lists(h->world->state, device);
+}
+
+long rt_camera_record_builds(const Rust_WorldHandle *h) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_camera_record_builds: null argument");
+        return -1;
+    }
+    std::lock_guard<std::recursive_mutex> lock(h->world->state.mu);
+    return (long)h->world->state.ctree_version;
+}
+
 // image.rs:59-81: "P3\n{w} {h}\n255\n" then "r g b\n" per pixel, top row first.
 int rt_write_ppm(const Rust_CFramebuffer *fb, const char *path) {
     if (!fb || !path || (!fb->pixels && fb->width * fb->height)) return -1;

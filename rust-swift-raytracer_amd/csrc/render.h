@@ -320,6 +320,20 @@ inline size_t adapt_compact_blocks(size_t n) { return (n + kAdaptBlock - 1) / kA
 hipError_t launch_sphere_lists(const float4 *prims, uint32_t n, const double *Mi, const double *o,
                                double e_abs, double wden, double hden, uint32_t width, uint32_t height,
                                int4 *rects, uint32_t *flag, uint2 *rec, hipStream_t stream);
+// Primary triangle strip lists built on the device (tri_lists.hip; bvh.h
+// build_primary_tri_lists, the same double arithmetic per record), in two
+// steps around one 8-byte readback that sizes `items`.  counts: boxes (6 n
+// floats, CameraTriangleBVH::rec_box) -> rects (n int4 of scratch), count
+// (strips x rows u32 of scratch), offsets (strips x rows + 1, the lists' CSR),
+// alw (n u32: the `always` records, ascending) and meta (4 u32: items in the
+// strips, `always` records, 1 if the total is out of range).  fill: items
+// [0, total) from the same loop as the counts, then the `always` records.
+hipError_t launch_tri_list_counts(const float *boxes, uint32_t n, const double *Mi, const double *o, double wden,
+                                  double hden, uint32_t width, uint32_t height, int4 *rects, uint32_t *count,
+                                  uint32_t *offsets, uint32_t *alw, uint32_t *meta, hipStream_t stream);
+hipError_t launch_tri_list_fill(const int4 *rects, uint32_t n, uint32_t width, uint32_t height,
+                                const uint32_t *offsets, const uint32_t *alw, uint32_t total, uint32_t nalways,
+                                uint32_t *items, hipStream_t stream);
 // SERIAL mode, the estimate reduction (render_frame_serial step 1), on the
 // device.  tab holds, for a frame of npix pixels (serial_tab_doubles(npix)):
 //   P   [0, npix]             prefix sums of spp mu (SerialPred::P)

@@ -54,9 +54,11 @@ DeviceState::~DeviceState() {
                     sph_shade, sph_kind, tbvh_nodes, tbvh_tris, tbvh_loose, tw_nodes, tw_tris,
                     cam_nodes, cam_tris, ptl_off, ptl_items, spl, tile, gath,
                     sstates, stab, sscan, swin, sjump, sctrl, sbend, spath, sfin,
-                    gspl, gspl_rects, gspl_flag, scheck, slo, ssbend, ssb, sptab, sspix, sptab2};
+                    gspl, gspl_rects, gspl_flag, scheck, slo, ssbend, ssb, sptab, sspix, sptab2,
+                    gptl_box, gptl_off, gptl_items, gptl_rects, gptl_count, gptl_alw, gptl_meta};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
+    if (gptl_hmeta) (void)hipHostFree(gptl_hmeta);
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : tev)
@@ -461,6 +463,100 @@ static int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel 
     return 0;
 }
 
+// Primary triangle strip lists are built on the device too (RT_AMD_GPU_TRI_LISTS,
+// default 1; 0: bvh.cpp build_primary_tri_lists on the host, then an upload),
+// from the camera-origin records' boxes, which change only with the origin: a
+// camera that turns in place uploads nothing.
+static bool gpu_tri_lists() { return env_u64("RT_AMD_GPU_TRI_LISTS", 1) != 0; }
+
+// d's device-built lists are those of (cam, width, height, w.ctree)
+static bool device_tri_lists_current(const WorldState &w, const DeviceState *d, const CameraModel &cam, size_t width,
+                                     size_t height) {
+    return d->gptl_built && d->gptl_w == width && d->gptl_h == height && d->gptl_ctree == w.ctree_version &&
+           same_cam(d->gptl_cam, cam);
+}
+
+// The device build of the primary triangle lists for (cam, width, height,
+// w.ctree), enqueued on s when any of them changed.  The lengths are read back
+// (8 bytes, pinned) to size the items, so the first frame after a change waits
+// on the host here, as it waited for the host build.  ok = false: no lists
+// (d->gptl_host: the sizes are beyond the kernels' range and the host builds).
+// RT_AMD_PTL_CHECK=1 (tests): compare the three arrays with the host build.
+static int device_tri_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
+                            hipStream_t s, bool &ok) {
+    if (!device_tri_lists_current(w, d, cam, width, height)) {
+        const CameraTriangleBVH &ct = w.ctree;
+        TriListParams tp;
+        d->gptl_built = false;
+        d->gptl_ok = tri_list_params(ct, cam, width, height, tp);
+        d->gptl_host = d->gptl_ok && ((height + 15) / 16 > 65535 ||
+                                      (uint64_t)tp.strips_per_row * height >= 0x7FFFFFFFull);
+        if (d->gptl_host) d->gptl_ok = false;
+        if (d->gptl_ok) {
+            const size_t ncells = (size_t)tp.strips_per_row * height;
+            if (d->gptl_box_version != w.ctree_version) {
+                HIP_TRY(grow(d->gptl_box, d->gptl_box_cap, ct.rec_box.size()));
+                HIP_TRY(hipMemcpyAsync(d->gptl_box, ct.rec_box.data(), ct.rec_box.size() * 4, hipMemcpyHostToDevice,
+                                       s));
+                // (rec_box is pageable and may be rebuilt by the next origin: wait for the copy)
+                HIP_TRY(hipStreamSynchronize(s));
+                d->gptl_box_version = w.ctree_version;
+            }
+            HIP_TRY(grow(d->gptl_rects, d->gptl_rects_cap, (size_t)tp.n));
+            HIP_TRY(grow(d->gptl_alw, d->gptl_alw_cap, (size_t)tp.n));
+            HIP_TRY(grow(d->gptl_count, d->gptl_count_cap, ncells));
+            HIP_TRY(grow(d->gptl_off, d->gptl_off_cap, ncells + 1));
+            HIP_TRY(grow(d->gptl_meta, d->gptl_meta_cap, 4));
+            if (!d->gptl_hmeta) HIP_TRY(hipHostMalloc((void **)&d->gptl_hmeta, 4 * sizeof(uint32_t)));
+            HIP_TRY(launch_tri_list_counts(d->gptl_box, tp.n, tp.Mi, tp.o, tp.wden, tp.hden, tp.width, tp.height,
+                                           d->gptl_rects, d->gptl_count, d->gptl_off, d->gptl_alw, d->gptl_meta, s));
+            HIP_TRY(hipMemcpyAsync(d->gptl_hmeta, d->gptl_meta, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            const uint32_t total = d->gptl_hmeta[0], nalways = d->gptl_hmeta[1];
+            if (d->gptl_hmeta[2] != 0 || nalways > tp.n) {  // (more items than the host's u32 offsets hold)
+                d->gptl_ok = false;
+                d->gptl_host = true;
+            } else {
+                HIP_TRY(grow(d->gptl_items, d->gptl_items_cap, std::max<size_t>((size_t)total + nalways, 1)));
+                HIP_TRY(launch_tri_list_fill(d->gptl_rects, tp.n, tp.width, tp.height, d->gptl_off, d->gptl_alw,
+                                             total, nalways, d->gptl_items, s));
+                d->gptl_spr = tp.strips_per_row;
+                d->gptl_total = total;
+                d->gptl_nalways = nalways;
+            }
+        }
+        if (d->gptl_ok && env_u64("RT_AMD_PTL_CHECK", 0)) {
+            const PrimaryTriLists h = build_primary_tri_lists(ct, cam, width, height);
+            const size_t nitems = (size_t)d->gptl_total + d->gptl_nalways;
+            std::vector<uint32_t> off(h.offsets.size()), items(nitems);
+            const bool shape = h.strips_per_row == d->gptl_spr && h.items.size() == nitems &&
+                               h.offsets.size() == (size_t)d->gptl_spr * height + 1;
+            if (shape) {
+                HIP_TRY(hipMemcpyAsync(off.data(), d->gptl_off, off.size() * 4, hipMemcpyDeviceToHost, s));
+                if (nitems)
+                    HIP_TRY(hipMemcpyAsync(items.data(), d->gptl_items, nitems * 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+            if (!shape || off != h.offsets || items != h.items || h.offsets.back() != d->gptl_total) {
+                set_error("RT_AMD_PTL_CHECK: device triangle lists differ from the host build (" +
+                          std::to_string(nitems) + " items, host " + std::to_string(h.items.size()) + ")");
+                return -2;
+            }
+        } else if (!d->gptl_ok && !d->gptl_host && env_u64("RT_AMD_PTL_CHECK", 0) &&
+                   !build_primary_tri_lists(ct, cam, width, height).offsets.empty()) {
+            set_error("RT_AMD_PTL_CHECK: the device build gave no lists where the host build has them");
+            return -2;
+        }
+        d->gptl_cam = cam;
+        d->gptl_w = width;
+        d->gptl_h = height;
+        d->gptl_ctree = w.ctree_version;
+        d->gptl_built = true;
+    }
+    ok = d->gptl_ok;
+    return 0;
+}
+
 int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t height,
                  const RtRenderOptions &o, uint32_t *d_out, hipStream_t stream,
                  RtRenderStats *stats, const SerialPass *sp, const uint32_t *d_replay, bool defer_stats,
@@ -611,7 +707,25 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     }
     const bool use_tbvh = d->tnodes > 0 && o.accel != RT_ACCEL_BRUTE;
     const bool want_ptl = width >= 2 && height >= 2 && env_u64("RT_AMD_PRIMARY_LISTS", 1) != 0;
-    if (use_tbvh) prepare_camera_lists(w, cam, width, height, want_ptl);
+    // the lists on the device (the records alone on the host).  The build reads
+    // its lengths back, which a capturing stream cannot do: a captured frame
+    // uses the device lists only when they are current, else the host build
+    bool gpu_ptl = use_tbvh && want_ptl && gpu_tri_lists();
+    bool capturing = false;
+    if (gpu_ptl && stream) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        capturing = hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    }
+    int ptl_where = 0;  // rt_primary_tri_lists: 0 none, 1 host build, 2 device build
+    if (use_tbvh && gpu_ptl) {
+        prepare_camera(w, cam, false);
+        if (capturing && !device_tri_lists_current(w, d, cam, width, height)) {
+            gpu_ptl = false;
+            prepare_camera_lists(w, cam, width, height, true);
+        }
+    } else if (use_tbvh) {
+        prepare_camera_lists(w, cam, width, height, want_ptl);
+    }
     if (use_tbvh && w.ctree_version && d->cam_version != w.ctree_version) {
         for (void *b : {(void *)d->cam_nodes, (void *)d->cam_tris})
             if (b) HIP_TRY(hipFree(b));
@@ -637,8 +751,25 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
                 p.cam_nodes = d->cam_nodes;
                 p.cam_nnodes = d->cam_nnodes;
             }
-            if (want_ptl && w.ptl_version && w.ptl_w == width && w.ptl_h == height &&
-                w.ptl_ctree == w.ctree_version && same_cam(w.ptl_cam, cam)) {
+            bool dev_lists = false;
+            if (gpu_ptl) {
+                rc = device_tri_lists(w, d, cam, width, height, s, dev_lists);
+                if (rc) return rc;
+                if (d->gptl_host) {  // (beyond the kernels' range)
+                    gpu_ptl = false;
+                    prepare_camera_lists(w, cam, width, height, true);
+                }
+            }
+            if (dev_lists) {
+                primary_lists = true;
+                ptl_where = 2;
+                p.ptl_off = d->gptl_off;
+                p.ptl_items = d->gptl_items;
+                p.ptl_spr = d->gptl_spr;
+                p.ptl_always = d->gptl_total;
+                p.ptl_end = d->gptl_total + d->gptl_nalways;
+            } else if (!gpu_ptl && want_ptl && w.ptl_version && w.ptl_w == width && w.ptl_h == height &&
+                       w.ptl_ctree == w.ctree_version && same_cam(w.ptl_cam, cam)) {
                 if (d->ptl_version != w.ptl_version) {
                     for (void *b : {(void *)d->ptl_off, (void *)d->ptl_items})
                         if (b) HIP_TRY(hipFree(b));
@@ -657,6 +788,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
                 }
                 if (d->ptl_off) {
                     primary_lists = true;
+                    ptl_where = 1;
                     p.ptl_off = d->ptl_off;
                     p.ptl_items = d->ptl_items;
                     p.ptl_spr = w.ptl.strips_per_row;
@@ -949,6 +1081,7 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
             else if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, corner_img, tail));
             else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, corner_img, leaf_defer));
             d->last_leaf_defer = trace_leaf_defer(tv);
+            d->last_ptl = ptl_where;
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
             d->cset_clean[d->cset] = true;
@@ -1658,6 +1791,14 @@ int leaf_defer(WorldState &w, int device) {
     int rc = device_for(w, device, d);
     if (rc) return rc;
     return d->last_leaf_defer;
+}
+
+int primary_tri_lists(WorldState &w, int device) {
+    std::lock_guard<std::recursive_mutex> lock(w.mu);  // (device_for may add a device)
+    DeviceState *d = nullptr;
+    int rc = device_for(w, device, d);
+    if (rc) return rc;
+    return d->last_ptl;
 }
 
 long read_samples(WorldState &w, int device, float *out, size_t n) {

@@ -72,6 +72,23 @@ struct DeviceState {
     CameraModel gspl_cam{};
     size_t gspl_w = 0, gspl_h = 0;
     bool gspl_built = false, gspl_ok = false;
+    // primary triangle strip lists built on the device (tri_lists.hip): the
+    // records' boxes (uploaded once per ctree_version), the lists, scratch
+    float *gptl_box = nullptr;       size_t gptl_box_cap = 0;
+    uint64_t gptl_box_version = 0;                             // WorldState::ctree_version uploaded
+    uint32_t *gptl_off = nullptr;    size_t gptl_off_cap = 0;
+    uint32_t *gptl_items = nullptr;  size_t gptl_items_cap = 0;
+    int4 *gptl_rects = nullptr;      size_t gptl_rects_cap = 0;
+    uint32_t *gptl_count = nullptr;  size_t gptl_count_cap = 0;
+    uint32_t *gptl_alw = nullptr;    size_t gptl_alw_cap = 0;
+    uint32_t *gptl_meta = nullptr;   size_t gptl_meta_cap = 0;
+    uint32_t *gptl_hmeta = nullptr;                            // (pinned: the lengths read back)
+    CameraModel gptl_cam{};
+    size_t gptl_w = 0, gptl_h = 0;
+    uint64_t gptl_ctree = 0;
+    uint32_t gptl_spr = 0, gptl_total = 0, gptl_nalways = 0;
+    bool gptl_built = false, gptl_ok = false, gptl_host = false;  // gptl_host: out of range, the host builds
+    int last_ptl = 0;                                          // rt_primary_tri_lists of the last launch
     size_t lds_bytes = 0;                                      // 0: tree not LDS-stageable
     // corner records (bvh.h SphereBVH::corner), uploaded when the sphere-only
     // frame kernels can stage them without losing a workgroup per CU
@@ -335,6 +352,8 @@ void prepare_camera(WorldState &w, const CameraModel &cam, bool tree = false);
 
 long read_samples(WorldState &w, int device, float *out, size_t n);
 int leaf_defer(WorldState &w, int device);
+// where the last frame launch's primary triangle lists were built (rt_primary_tri_lists)
+int primary_tri_lists(WorldState &w, int device);
 
 size_t tile_rows(size_t height, uint32_t row_block, uint32_t rank, uint32_t nranks);
 size_t tile_row(size_t k, uint32_t row_block, uint32_t rank, uint32_t nranks);

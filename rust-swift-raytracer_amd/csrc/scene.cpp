@@ -185,6 +185,50 @@ CameraModel camera_moved(const CameraModel &c, float x, float y, float z) {
     return camera_new_at(vadd(c.origin, {x, y, z}), aspect);
 }
 
+// camera.rs:34-48.  f32::tan is the platform libm's tanf, so is this one.
+CameraModel camera_with_vertical_fov(Vec3 origin, float vertical_fov, float aspect) {
+    const float h = tanf(vertical_fov / 2.0f);
+    const float viewport_height = 2.0f * h;
+    const float viewport_width = aspect * viewport_height;
+    const float focal_length = 1.0f;
+    CameraModel c;
+    c.origin = origin;
+    c.horizontal = {viewport_width, 0.0f, 0.0f};
+    c.vertical = {0.0f, viewport_height, 0.0f};
+    c.lower_left = vsub(origin, {viewport_width / 2.0f, viewport_height / 2.0f, focal_length});
+    return c;
+}
+
+// camera.rs:49-69.  u and v are the raw cross products (NVec3::cross builds
+// them with new_unchecked, maths.rs:131-137): not renormalised.
+int camera_look_at(Vec3 origin, Vec3 look_at, Vec3 up, float vertical_fov, float aspect, CameraModel &out) {
+    const Vec3 d = vsub(origin, look_at);
+    const float s = 1e-8f;  // maths.rs:46-49 near_zero
+    if (std::fabs(d.x) < s && std::fabs(d.y) < s && std::fabs(d.z) < s) return 1;
+    const float viewport_height = 2.0f * tanf(vertical_fov / 2.0f);
+    const float viewport_width = viewport_height * aspect;
+    const Vec3 w = vnormalize(d);
+    const Vec3 u = vcross(vnormalize(up), w);  // `up` arrives as an NVec3 (NVec3::new)
+    const Vec3 v = vcross(w, u);
+    if (!(std::fabs(v.y) > 1e-8f)) return 2;
+    const Vec3 horizontal = {u.x * viewport_width, u.y * viewport_width, u.z * viewport_width};
+    const Vec3 vertical = {v.x * viewport_height, v.y * viewport_height, v.z * viewport_height};
+    const Vec3 h2 = {horizontal.x / 2.0f, horizontal.y / 2.0f, horizontal.z / 2.0f};
+    const Vec3 v2 = {vertical.x / 2.0f, vertical.y / 2.0f, vertical.z / 2.0f};
+    out.origin = origin;
+    out.horizontal = horizontal;
+    out.vertical = vertical;
+    out.lower_left = vsub(vsub(vsub(origin, h2), v2), w);
+    return 0;
+}
+
+CameraModel camera_translated(const CameraModel &c, float x, float y, float z) {
+    CameraModel t = c;
+    t.origin = vadd(c.origin, {x, y, z});
+    t.lower_left = vadd(c.lower_left, {x, y, z});
+    return t;
+}
+
 int parse_scene(const std::string &text, SceneModel &out) {
     if (!valid_utf8(text)) return kWouldPanic;  // CStr::to_str().unwrap(), lib.rs:39
     out = SceneModel{};

@@ -35,6 +35,14 @@ CameraModel camera_new_at(Vec3 origin, float aspect);
 // lib.rs:60-63 (+ camera.rs:70-72 aspect_ratio, :91-93 position)
 CameraModel camera_moved(const CameraModel &c, float x, float y, float z);
 
+// camera.rs:34-48: new_at with a vertical field of view (radians), looking down -z
+CameraModel camera_with_vertical_fov(Vec3 origin, float vertical_fov, float aspect);
+// camera.rs:49-69, every step one f32 operation in its order.  Returns 0, or the
+// reference's failed assert: 1 near_zero(origin - look_at), 2 !(|v.y| > 1e-8).
+int camera_look_at(Vec3 origin, Vec3 look_at, Vec3 up, float vertical_fov, float aspect, CameraModel &out);
+// origin and lower_left moved by (x, y, z); the orientation and the viewport stay
+CameraModel camera_translated(const CameraModel &c, float x, float y, float z);
+
 struct SceneModel {
     std::vector<Material> materials;   // one entry per sphere/triangle reference
     std::vector<Sphere> spheres;       // in file order (ties: first wins)

@@ -36,6 +36,8 @@ EXPORTS = (
     "rt_accum_samples", "rt_accum_read", "rt_accum_reset", "rt_accum_free",
     "rt_adapt_default_options", "rt_adapt_enable", "rt_adapt_disable", "rt_adapt_active",
     "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active", "rt_leaf_defer",
+    "rt_camera_new_with_vertical_fov", "rt_camera_new_look_at", "rt_camera_from_floats",
+    "rt_camera_translate", "rt_camera_free", "rt_primary_tri_lists", "rt_camera_record_builds",
 )
 
 
@@ -171,6 +173,21 @@ def lib(path=None):
         if hasattr(L, "rt_leaf_defer"):  # (an older build loaded for an A/B run has none)
             L.rt_leaf_defer.restype = C.c_int
             L.rt_leaf_defer.argtypes = [H, C.c_int]
+        if hasattr(L, "rt_camera_new_look_at"):  # (likewise)
+            L.rt_camera_new_with_vertical_fov.restype = C.c_void_p
+            L.rt_camera_new_with_vertical_fov.argtypes = [fp, C.c_float, C.c_float]
+            L.rt_camera_new_look_at.restype = C.c_void_p
+            L.rt_camera_new_look_at.argtypes = [fp, fp, fp, C.c_float, C.c_float]
+            L.rt_camera_from_floats.restype = C.c_void_p
+            L.rt_camera_from_floats.argtypes = [fp]
+            L.rt_camera_translate.restype = C.c_void_p
+            L.rt_camera_translate.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+            L.rt_camera_free.restype = None
+            L.rt_camera_free.argtypes = [C.c_void_p]
+            L.rt_primary_tri_lists.restype = C.c_int
+            L.rt_primary_tri_lists.argtypes = [H, C.c_int]
+            L.rt_camera_record_builds.restype = C.c_long
+            L.rt_camera_record_builds.argtypes = [H]
         if hasattr(L, "rt_accum_create"):  # (an older build loaded for an A/B run has none)
             L.rt_accum_default_options.argtypes = [C.POINTER(AccumOptions)]
             L.rt_accum_create.restype = C.c_void_p
@@ -260,6 +277,17 @@ def options(spp=16, depth=8, mode=RNG_COUNTER, seed=DEFAULT_SEED, replay=None, r
     return o, keep
 
 
+def _vec3(v):
+    a = np.ascontiguousarray(v, dtype=np.float32)
+    if a.size != 3:
+        raise ValueError("a point or vector is 3 floats")
+    return a
+
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
 class World:
     """A loaded world: load_world (lib.rs:37-46) + camera moves + rendering."""
 
@@ -322,6 +350,49 @@ class World:
     def move_camera(self, x, y, z):
         """GameView.swift:200-216: handle.camera = move_camera_position(camera, ...)."""
         self._h.contents.camera = self._L.move_camera_position(self._h.contents.camera, x, y, z)
+
+    def _swap_camera(self, cam, what):
+        """The header's pattern: if (c) { rt_camera_free(h->camera); h->camera = c; }"""
+        if not cam:
+            raise ValueError(f"{what} failed: {self._L.rt_last_error().decode()}")
+        self._L.rt_camera_free(self._h.contents.camera)
+        self._h.contents.camera = cam
+
+    def look_at(self, origin, target, up=(0.0, 1.0, 0.0), vfov=np.pi / 2, aspect=1.5):
+        """rt_camera_new_look_at (camera.rs:49-69): the camera at `origin` facing
+        `target`; vfov in radians.  ValueError where the reference asserts."""
+        o, t, u = (_vec3(v) for v in (origin, target, up))
+        self._swap_camera(self._L.rt_camera_new_look_at(_fp(o), _fp(t), _fp(u), vfov, aspect), "look_at")
+
+    def vertical_fov(self, origin, vfov, aspect=1.5):
+        """rt_camera_new_with_vertical_fov (camera.rs:34-48): looking down -z."""
+        o = _vec3(origin)
+        self._swap_camera(self._L.rt_camera_new_with_vertical_fov(_fp(o), vfov, aspect), "vertical_fov")
+
+    def set_camera(self, cam12):
+        """rt_camera_from_floats: the 12 floats of camera(), bits as given (what a
+        tiles.py rank or a second World needs to share this one's view)."""
+        c = np.ascontiguousarray(cam12, dtype=np.float32)
+        if c.size != 12:
+            raise ValueError("a camera is 12 floats")
+        self._swap_camera(self._L.rt_camera_from_floats(_fp(c)), "set_camera")
+
+    def translate_camera(self, x, y, z):
+        """rt_camera_translate: moves the camera and keeps its orientation
+        (move_camera rebuilds a -z camera, as the reference does)."""
+        self._h.contents.camera = self._L.rt_camera_translate(self._h.contents.camera, x, y, z)
+
+    def primary_tri_lists(self, device=-1):
+        """rt_primary_tri_lists: where the last frame launch's primary triangle
+        lists were built (0 none, 1 host, 2 device)."""
+        n = self._L.rt_primary_tri_lists(self._h, device)
+        if n < 0:
+            raise RenderError(f"rt_primary_tri_lists failed ({n}): {self._L.rt_last_error().decode()}")
+        return n
+
+    def camera_record_builds(self):
+        """rt_camera_record_builds: builds of the camera-origin triangle records so far."""
+        return int(self._L.rt_camera_record_builds(self._h))
 
     def render_reference(self, width, height):
         """The reference ABI call render(fb, handle): 16 spp, depth 8 (lib.rs:49-57)."""
