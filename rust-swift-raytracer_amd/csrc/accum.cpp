@@ -1,0 +1,369 @@
+// accum.cpp -- progressive and adaptive accumulation, host side (rt_accum_*,
+// rt_adapt_*: DESIGN.md 5.6, 5.7): an accumulator's lifetime, its passes
+// through render_frame and its reads.
+#include <algorithm>
+
+#include "runtime_internal.h"
+
+namespace rtamd {
+
+// ------------------------------------------------------------ accumulation
+// (rt_accum_*: DESIGN.md 5.6)
+namespace {
+// guards AccumState::world and WorldState::accums (a world freed before its
+// accumulators detaches them)
+std::mutex g_accum_mu;
+
+void camera_floats(const CameraModel &cam, float out[12]) {
+    const Vec3 cv[4] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical};
+    for (int i = 0; i < 4; ++i) { out[3 * i] = cv[i].x; out[3 * i + 1] = cv[i].y; out[3 * i + 2] = cv[i].z; }
+}
+
+WorldState *accum_world(AccumState &a) {
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    if (!a.world) set_error("accumulator: its world was freed");
+    return a.world;
+}
+
+// The held samples count only for the camera and scene they were traced with
+// (the 12 camera floats compared as bits: a camera moved away and back matches)
+void accum_check_state(AccumState &a, WorldState &w, const float cam[12]) {
+    if (a.held != 0 && (std::memcmp(a.cam, cam, sizeof(a.cam)) != 0 || a.edit_version != w.edit_version)) a.held = 0;
+}
+
+void accum_release(AccumState *a) {
+    if (a->device >= 0 && hipSetDevice(a->device) == hipSuccess) {
+        // (the last pass may still write the buffers that delete frees)
+        if (a->done_stream) (void)hipEventSynchronize(a->done);
+        if (a->done) (void)hipEventDestroy(a->done);
+    }
+    delete a;
+}
+}  // namespace
+
+WorldState::~WorldState() {
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    for (AccumState *a : accums) a->world = nullptr;
+}
+
+AccumState *accum_create(WorldState &w, size_t width, size_t height, uint32_t stride, int32_t depth,
+                         uint32_t mode, uint32_t seed, const uint32_t *replay_states, int32_t device,
+                         int32_t accel) {
+    if (width == 0 || height == 0 || width > 0xFFFFFFu || height > 0xFFFFFFu ||
+        (uint64_t)width * height > 0xFFFFFFFFull) {
+        set_error("rt_accum_create: frame size must be 1 x 1 to 2^24 - 1 squared, below 2^32 pixels");
+        return nullptr;
+    }
+    if (stride == 0) { set_error("rt_accum_create: sample_stride must be at least 1"); return nullptr; }
+    if (mode == RT_RNG_SERIAL) {
+        set_error("rt_accum_create: RT_RNG_SERIAL cannot be accumulated (one stream over the whole frame "
+                  "has no per-pass meaning); use RT_RNG_COUNTER or RT_RNG_REPLAY");
+        return nullptr;
+    }
+    if (mode != RT_RNG_COUNTER && mode != RT_RNG_REPLAY) {
+        set_error("rt_accum_create: rng_mode must be RT_RNG_COUNTER or RT_RNG_REPLAY");
+        return nullptr;
+    }
+    if (mode == RT_RNG_REPLAY && !replay_states) {
+        set_error("rt_accum_create: replay table missing");
+        return nullptr;
+    }
+    std::lock_guard<std::recursive_mutex> lock(w.mu);
+    DeviceState *d = nullptr;
+    if (device_for(w, device, d)) return nullptr;
+    AccumState *a = new AccumState();
+    a->width = width; a->height = height; a->stride = stride;
+    a->depth = depth; a->device = d->device; a->accel = accel;
+    a->mode = mode; a->seed = seed;
+    auto fail = [&](hipError_t e, const char *what) -> AccumState * {
+        set_error(std::string("rt_accum_create: ") + what + " failed: " + hipGetErrorString(e));
+        accum_release(a);
+        return nullptr;
+    };
+    hipError_t e = hipEventCreateWithFlags(&a->done, hipEventDisableTiming);
+    if (e != hipSuccess) return fail(e, "hipEventCreate");
+    e = a->sums.grow(3 * width * height);
+    if (e != hipSuccess) return fail(e, "allocating the sums");
+    if (mode == RT_RNG_REPLAY) {
+        const size_t n = width * height * (size_t)stride;
+        e = a->replay.grow(n);
+        if (e != hipSuccess) return fail(e, "allocating the replay table");
+        e = hipMemcpy(a->replay.get(), replay_states, n * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(e, "hipMemcpy (replay table)");
+    }
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    a->world = &w;
+    w.accums.push_back(a);
+    return a;
+}
+
+void accum_free(AccumState *a) {
+    if (!a) return;
+    {
+        std::lock_guard<std::mutex> g(g_accum_mu);
+        if (a->world) {
+            auto &v = a->world->accums;
+            v.erase(std::remove(v.begin(), v.end(), a), v.end());
+            a->world = nullptr;
+        }
+    }
+    accum_release(a);
+}
+
+int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t *d_out, hipStream_t stream,
+              void *host_out, RtRenderStats *stats) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    WorldState &w = *wp;
+    std::lock_guard<std::recursive_mutex> lock(w.mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, w, cf);
+    if (nsamples <= 0) { set_error("rt_accum_add: nsamples must be at least 1"); return -1; }
+    if ((uint64_t)nsamples > (uint64_t)(a.stride - a.held)) {
+        set_error("rt_accum_add: " + std::to_string(a.held) + " + " + std::to_string(nsamples) +
+                  " samples exceed the accumulator's sample_stride " + std::to_string(a.stride));
+        return -1;
+    }
+    DeviceState *d = nullptr;
+    int rc = device_for(w, a.device, d);
+    if (rc) return rc;
+    hipStream_t s = stream ? stream : d->stream;
+    const size_t npix = a.width * a.height;
+    // (an adaptive accumulator's passes write its own frame, which is copied out below)
+    uint32_t *const d_user = d_out;
+    if (a.adaptive) {
+        d_out = a.frame.get();
+    } else if (!d_out) {  // (the kernels always write the frame)
+        HIP_TRY(d->out.grow(npix));
+        d_out = d->out.get();
+    }
+    RtRenderOptions o;
+    std::memset(&o, 0, sizeof(o));
+    o.max_ray_bounces = a.depth;
+    o.rng_mode = a.mode;
+    o.seed = a.seed;
+    o.nranks = 1;
+    o.device = a.device;
+    o.accel = a.accel;
+    std::memcpy(a.cam, cf, sizeof(cf));
+    a.edit_version = w.edit_version;
+    // a ring slot holds whole pixels of at most 4096 samples: larger requests
+    // run as consecutive passes (the same fold, continued)
+    uint32_t left = (uint32_t)nsamples;
+    RtRenderStats total{};
+    while (left) {
+        const uint32_t n = std::min<uint32_t>(left, 4096u);
+        o.samples_per_pixel = (int32_t)n;
+        AccumPass ap{&a, a.held};
+        if (a.adaptive) {
+            if (a.held == 0) {  // (render_frame fills the list and zeroes the planes)
+                a.cur = 0;
+                a.nactive = (uint32_t)npix;
+            }
+            // an empty list: nothing is traced and N stays (the frame is still delivered)
+            if (a.nactive == 0) break;
+            ap.list = a.list[a.cur].get();
+            ap.nactive = a.nactive;
+        }
+        RtRenderStats st{};
+        rc = render_frame(w, cam, a.width, a.height, o, d_out, s, stats ? &st : nullptr, nullptr, a.replay.get(), false,
+                          &ap);
+        if (rc) return rc;
+        a.held += n;
+        left -= n;
+        if (a.adaptive) {
+            // the pass's decision: counts, and from min_samples
+            // on the converged pixels leave the list; the new length is read
+            // back, so the host waits for the pass here
+            const bool decide = a.held >= a.min_samples;
+            HIP_TRY(launch_adapt_select(a.list[a.cur].get(), a.nactive, a.sums.get(), a.sumsq.get(), npix,
+                                        a.count.get(), a.keep.get(), a.held, 1.0f / (float)a.held, a.tolerance,
+                                        a.bias, decide, s));
+            if (decide) {
+                HIP_TRY(launch_adapt_compact(a.list[a.cur].get(), a.keep.get(), a.nactive, a.totals.get(),
+                                             a.list[a.cur ^ 1u].get(), a.d_len.get(), s));
+                HIP_TRY(hipMemcpyAsync(a.h_len.get(), a.d_len.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            }
+            HIP_TRY(hipEventRecord(a.done, s));
+            a.done_stream = s;
+            if (decide) {
+                HIP_TRY(hipStreamSynchronize(s));
+                a.cur ^= 1u;
+                a.nactive = *a.h_len.get();
+            }
+        }
+        if (stats) {
+            const uint64_t samples = total.samples + st.samples;
+            const double ms = total.trace_ms + st.trace_ms, rms = total.resolve_ms + st.resolve_ms;
+            const uint32_t launches = total.trace_launches + st.trace_launches;
+            total = st;  // (schedule and path: the last pass's)
+            total.samples = samples;
+            total.trace_ms = ms;
+            total.resolve_ms = rms;
+            total.trace_launches = launches;
+        }
+    }
+    if (stats) *stats = total;
+    if (a.adaptive) {
+        // (a call that traced nothing still orders the copies after the last pass)
+        if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
+        if (d_user) HIP_TRY(hipMemcpyAsync(d_user, a.frame.get(), npix * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (host_out) {
+        HIP_TRY(hipMemcpyAsync(host_out, d_out, npix * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+long accum_samples(AccumState &a, const CameraModel &cam) {
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    std::lock_guard<std::recursive_mutex> lock(wp->mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, *wp, cf);
+    return (long)a.held;
+}
+
+int accum_read(AccumState &a, const CameraModel &cam, float *sums) {
+    if (!sums) { set_error("rt_accum_read: null output"); return -1; }
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    std::lock_guard<std::recursive_mutex> lock(wp->mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, *wp, cf);
+    const size_t npix = a.width * a.height;
+    if (a.held == 0) {  // (a reset only sets N: the next pass zero-fills the planes)
+        std::fill(sums, sums + 3 * npix, 0.0f);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(a.device));
+    HIP_TRY(hipEventSynchronize(a.done));
+    std::vector<float> planes(3 * npix);
+    HIP_TRY(hipMemcpy(planes.data(), a.sums.get(), 3 * npix * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i)
+        for (size_t c = 0; c < 3; ++c) sums[3 * i + c] = planes[c * npix + i];
+    return 0;
+}
+
+int accum_reset(AccumState &a) {
+    WorldState *wp = accum_world(a);
+    if (!wp) return -1;
+    std::lock_guard<std::recursive_mutex> lock(wp->mu);
+    a.held = 0;
+    return 0;
+}
+
+// ------------------------------------------------------------ adaptive accumulation
+// (rt_adapt_*: DESIGN.md 5.7)
+namespace {
+// the accumulator's world, locked, after the reset rule; nullptr with the error set
+WorldState *adapt_begin(AccumState &a, const CameraModel &cam, std::unique_lock<std::recursive_mutex> &lock) {
+    WorldState *wp = accum_world(a);
+    if (!wp) return nullptr;
+    lock = std::unique_lock<std::recursive_mutex>(wp->mu);
+    float cf[12];
+    camera_floats(cam, cf);
+    accum_check_state(a, *wp, cf);
+    return wp;
+}
+}  // namespace
+
+int adapt_enable(AccumState &a, const CameraModel &cam, float tolerance, float bias, uint32_t min_samples) {
+    // (the options were checked by rt_adapt_enable, before the accumulator)
+    std::unique_lock<std::recursive_mutex> lock;
+    WorldState *wp = adapt_begin(a, cam, lock);
+    if (!wp) return -1;
+    if (a.held != 0) {
+        set_error("rt_adapt_enable: the accumulator holds " + std::to_string(a.held) + " samples (reset it first)");
+        return -1;
+    }
+    if (!a.frame) {
+        HIP_TRY(hipSetDevice(a.device));
+        const size_t npix = a.width * a.height;
+        // (an enable that failed half way keeps what it got: the next one goes on, release frees it)
+        HIP_TRY(a.sumsq.grow(npix));
+        HIP_TRY(a.count.grow(npix));
+        HIP_TRY(a.list[0].grow(npix));
+        HIP_TRY(a.list[1].grow(npix));
+        HIP_TRY(a.keep.grow(npix));
+        HIP_TRY(a.totals.grow(adapt_compact_blocks(npix)));
+        HIP_TRY(a.d_len.grow(1));
+        HIP_TRY(a.h_len.grow(1));
+        HIP_TRY(a.frame.grow(npix));  // (last: its presence means all are)
+    }
+    a.adaptive = true;
+    a.tolerance = tolerance;
+    a.bias = bias;
+    a.min_samples = min_samples;
+    return 0;
+}
+
+int adapt_disable(AccumState &a, const CameraModel &cam) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    if (a.held != 0) {
+        set_error("rt_adapt_disable: the accumulator holds " + std::to_string(a.held) + " samples (reset it first)");
+        return -1;
+    }
+    a.adaptive = false;
+    return 0;
+}
+
+long adapt_active(AccumState &a, const CameraModel &cam) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    return a.adaptive && a.held != 0 ? (long)a.nactive : (long)(a.width * a.height);
+}
+
+namespace {
+// one adaptive plane (4-byte elements) to the host; all zero with no samples held
+int adapt_read_plane(AccumState &a, const CameraModel &cam, bool counts, void *out, const char *who) {
+    if (!out) { set_error(std::string(who) + ": null output"); return -1; }
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!a.adaptive) { set_error(std::string(who) + ": the accumulator is not adaptive"); return -1; }
+    const size_t npix = a.width * a.height;
+    if (a.held == 0) {
+        std::memset(out, 0, npix * 4);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(a.device));
+    HIP_TRY(hipEventSynchronize(a.done));
+    HIP_TRY(hipMemcpy(out, counts ? (const void *)a.count.get() : (const void *)a.sumsq.get(), npix * 4,
+                      hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // namespace
+
+int adapt_read_counts(AccumState &a, const CameraModel &cam, uint32_t *counts) {
+    return adapt_read_plane(a, cam, true, counts, "rt_adapt_read_counts");
+}
+
+int adapt_read_sumsq(AccumState &a, const CameraModel &cam, float *sumsq) {
+    return adapt_read_plane(a, cam, false, sumsq, "rt_adapt_read_sumsq");
+}
+
+long adapt_read_active(AccumState &a, const CameraModel &cam, uint32_t *list, size_t cap) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!a.adaptive) { set_error("rt_adapt_read_active: the accumulator is not adaptive"); return -1; }
+    const size_t npix = a.width * a.height;
+    if (a.held == 0) {  // (every pixel, ascending: what the next pass starts from)
+        for (size_t i = 0; list && i < std::min(cap, npix); ++i) list[i] = (uint32_t)i;
+        return (long)npix;
+    }
+    const size_t n = std::min<size_t>(cap, a.nactive);
+    if (list && n) {
+        HIP_TRY(hipSetDevice(a.device));
+        HIP_TRY(hipEventSynchronize(a.done));
+        HIP_TRY(hipMemcpy(list, a.list[a.cur].get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return (long)a.nactive;
+}
+
+}  // namespace rtamd

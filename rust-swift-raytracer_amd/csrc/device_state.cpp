@@ -1,0 +1,288 @@
+// device_state.cpp -- a world's state on one device: stream and events, the
+// scene upload (once per device, reused by every frame and every camera
+// move), and the LDS layout and occupancy decisions for the scene's kernel
+// instances.  Also the thread's error string.
+#include <algorithm>
+
+#include "runtime_internal.h"
+
+namespace rtamd {
+
+namespace {
+thread_local std::string g_error;
+}  // namespace
+
+void set_error(const std::string &msg) { g_error = msg; }
+const std::string &last_error() { return g_error; }
+
+DeviceState::~DeviceState() {
+    if (device < 0) return;
+    if (hipSetDevice(device) != hipSuccess) return;
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : tev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sev)
+        if (e) (void)hipEventDestroy(e);
+    if (done) (void)hipEventDestroy(done);
+    if (stream) (void)hipStreamDestroy(stream);
+    // (the buffers free themselves next, as members, on this device)
+}
+
+static int create_stream_and_events(DeviceState *d) {
+    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    for (auto &e : d->ev) HIP_TRY(hipEventCreate(&e));
+    for (auto &e : d->sev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventCreateWithFlags(&d->done, hipEventDisableTiming));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, d->device));
+    d->num_cus = prop.multiProcessorCount;
+    return 0;
+}
+
+// The scene's arrays and its sphere tree (once per device); the LDS trees'
+// records follow in choose_lds_layout, the triangle trees after it.
+static int upload_scene(const WorldState &w, DeviceState *d) {
+    const PackedScene &p = w.packed;
+    HIP_TRY(d->sph_hot.upload(p.sph_hot));
+    HIP_TRY(d->sph_cold.upload(p.sph_cold));
+    HIP_TRY(d->tri_hot.upload(p.tri_hot));
+    HIP_TRY(d->tri_geo.upload(p.tri_geo));
+    HIP_TRY(d->mats.upload(p.mats));
+    HIP_TRY(d->sph_shade.upload(p.sph_shade));
+    HIP_TRY(d->sph_kind.upload(p.sph_kind));
+    d->nsph = p.nsph;
+    d->nsph_padded = p.nsph_padded;
+    d->ntri = p.ntri;
+    const SphereBVH &bv = w.bvh;
+    if (!bv.nodes.empty()) {
+        std::vector<float> big_hot;
+        for (uint32_t i : bv.big)
+            for (int k = 0; k < 4; ++k) big_hot.push_back(p.sph_hot[(size_t)i * 4 + k]);
+        if (big_hot.empty()) big_hot.assign(4, 0.0f);
+        HIP_TRY(d->bvh_nodes.upload(bv.nodes));
+        HIP_TRY(d->bvh_prims.upload(bv.prims));
+        HIP_TRY(d->big_hot.upload(big_hot));
+        // (the kernels get these pointers even where the arrays are empty)
+        HIP_TRY(d->bvh_miss.upload(bv.miss, 1));
+        HIP_TRY(d->bvh_prim_id.upload(bv.prim_id, 1));
+        HIP_TRY(d->big_id.upload(bv.big, 1));
+        d->nnodes = (uint32_t)(bv.nodes.size() / 8);
+        d->nbig = (uint32_t)bv.big.size();
+        d->nprims = (uint32_t)bv.prim_id.size();
+    }
+    return 0;
+}
+
+// The triangle trees: the static one and, for a scene whose frames walk it
+// (d->tw_depth, set by choose_lds_layout), its 4-wide image.
+static int upload_triangle_trees(const WorldState &w, DeviceState *d) {
+    const TriangleBVH &tb = w.tbvh;
+    if (tb.nodes.empty()) return 0;
+    HIP_TRY(d->tbvh_nodes.upload(tb.qnodes, 1));
+    HIP_TRY(d->tbvh_tris.upload(tb.tris));
+    HIP_TRY(d->tbvh_loose.upload(tb.loose, 1));
+    d->tnodes = (uint32_t)(tb.qnodes.size() / 8);
+    if (d->tw_depth) {
+        if (w.tcells.ncells) {  // the per-cell trees + the static one
+            HIP_TRY(d->tw_nodes.upload(w.tcells.wnodes, 1));
+            HIP_TRY(d->tw_tris.upload(w.tcells.tris));
+        } else {
+            HIP_TRY(d->tw_nodes.upload(tb.wnodes, 1));
+        }
+    }
+    d->ttris = (uint32_t)(tb.tris.size() / 16);
+    d->tloose = (uint32_t)tb.loose.size();
+    return 0;
+}
+
+// Which sphere tree the scene's kernels stage in LDS (corner records, box
+// records or none), whether its frames walk the wide triangle image
+// (d->tw_depth != 0), and the resident workgroups per CU of every instance
+// (d->occupancy).  The part to read when a kernel's register count changes.
+// Runs after upload_scene (d->nnodes, d->nprims) and uploads the records of
+// the layouts it accepts (bvh_corner with corner_bytes, bvh_miss16 with
+// lds_bytes).
+static int choose_lds_layout(const WorldState &w, DeviceState *d, size_t lds_cap) {
+    // the scene's kernel family (render.h trace_mesh_kind; frames rendered with
+    // RT_ACCEL_BRUTE run the brute-force triangle kernels on these figures)
+    // Triangle trees are walked through their 4-wide image (kMesh 3) when it
+    // exists and every lane's stack fits in LDS beside a workgroup's tree
+    // (RT_AMD_TRI_WIDE=0: the binary walk)
+    const TriangleBVH &tw = w.tbvh;
+    const uint32_t tw_depth = std::max<uint32_t>(1u, 3u * std::max(tw.wdepth, w.tcells.wdepth));
+    bool wide = !tw.wnodes.empty() && env_u64("RT_AMD_TRI_WIDE", 1) != 0 &&
+                (size_t)tw_depth * trace_block_threads(trace_variant(kSearchLdsBox, false, 3, kKindLean)) * 2u <=
+                    64u * 1024u;
+    int tri = wide ? 3 : trace_mesh_kind(w.packed.ntri > 0, !w.tbvh.nodes.empty());
+    // the instance of kind c this scene runs with sphere search `search`
+    auto variant = [&](int search, int st, int c) { return trace_variant(search, st != 0, tri, c); };
+    // the wide walk's stacks in LDS
+    auto stack_lds = [&](TraceVariant v) -> size_t {
+        return v.mesh == 3 ? (size_t)tw_depth * trace_block_threads(v) * 2u : 0u;
+    };
+    // workgroups per CU of the kernels without the LDS sphere tree
+    auto occupancy_global = [&]() -> hipError_t {
+        for (int c = 0; c < 3; ++c)
+            for (int st = 0; st < 2; ++st)
+                for (int search : {kSearchBrute, kSearchGlobal}) {
+                    const TraceVariant v = variant(search, st, c);
+                    const hipError_t e = trace_occupancy(&d->occupancy(v), v, stack_lds(v));
+                    if (e != hipSuccess) return e;
+                }
+        return hipSuccess;
+    };
+    HIP_TRY(occupancy_global());
+    const SphereBVH &bv = w.bvh;
+    if (!bv.nodes.empty()) {
+        // LDS copy of the tree: 64 B per node + 20 B per sphere, u16 links
+        TraceParams lp{};
+        lp.nnodes = d->nnodes; lp.nprims = d->nprims; lp.nsph_padded = (uint32_t)w.packed.nsph_padded;
+        const size_t lds = trace_lds_bytes(lp);
+        // A tree above the 64 KB every kernel may take by default is staged
+        // only while it costs no workgroup: 160 KiB per CU are shared by the
+        // resident workgroups, so the instance must keep the workgroups per
+        // CU it has at 64 KB (the lean sphere kernel: 2 x 1024 threads, i.e.
+        // 80 KB each; losing one costs far more than the LDS walk saves).
+        // bytes: the workgroup's whole request; with the wide triangle
+        // walk's stacks in it (mesh 3) the 64 KB rule stays as it was.
+        auto keeps_workgroups = [&](TraceVariant v, size_t bytes, bool &ok) -> hipError_t {
+            const int blocks = d->occupancy(v);
+            ok = blocks > 0;
+            if (!ok || bytes <= kLdsDefaultMax) return hipSuccess;
+            ok = false;
+            if (v.mesh == 3) return hipSuccess;
+            int ref = 0;
+            const hipError_t e = trace_occupancy(&ref, v, kLdsDefaultMax);
+            ok = e == hipSuccess && blocks == ref;
+            return e;
+        };
+        // Corner records (bvh.h SphereBVH::corner) for the sphere-only frame
+        // kernels, lean and counting: 128 B per node, the shading records
+        // left in global memory
+        const size_t corner = trace_corner_lds(d->nnodes, d->nprims);
+        if (!bv.corner.empty() && tri == 0 && corner <= lds_cap) {
+            bool fits = true;
+            for (int c = 0; c < 2 && fits; ++c)
+                for (int st = 0; st < 2 && fits; ++st) {
+                    // (a query the runtime refuses: the layout does not fit)
+                    const TraceVariant v = variant(kSearchLdsCorner, st, c);
+                    if (trace_occupancy(&d->occupancy(v), v, corner) != hipSuccess ||
+                        keeps_workgroups(v, corner, fits) != hipSuccess) {
+                        (void)hipGetLastError();
+                        fits = false;
+                    }
+                }
+            if (fits) {
+                // (the deferred-leaf lean instance, where the build has one)
+                const TraceVariant v = trace_variant(kSearchLdsCorner, false, tri, kKindLean, true);
+                if (trace_leaf_defer(v) != 0 &&
+                    (trace_occupancy(&d->occupancy(v), v, corner) != hipSuccess ||
+                     keeps_workgroups(v, corner, fits) != hipSuccess)) {
+                    (void)hipGetLastError();
+                    fits = false;
+                }
+            }
+            if (fits) {
+                HIP_TRY(d->bvh_corner.upload(bv.corner));
+                d->corner_bytes = corner;
+            }
+        }
+        // (the LDS copy addresses 64-B node records with u16 byte offsets)
+        if (d->nnodes <= kLdsTreeMaxNodes && lds <= lds_cap) {
+            std::vector<uint16_t> m16(bv.miss.size());
+            for (size_t i = 0; i < m16.size(); ++i)
+                m16[i] = bv.miss[i] == kNodeEnd ? (uint16_t)0xFFFF : (uint16_t)bv.miss[i];
+            HIP_TRY(d->bvh_miss16.upload(m16));
+            // every kernel kind must fit its LDS (the tree, plus the wide
+            // walk's stacks for the frame kinds); when the stacks are what
+            // does not fit, the frames take the binary triangle walk and
+            // every kind keeps the LDS sphere tree
+            auto occupancy_lds = [&](bool &fits) -> hipError_t {
+                fits = true;
+                for (int c = 0; c < 3; ++c)
+                    for (int st = 0; st < 2; ++st) {
+                        const TraceVariant v = variant(kSearchLdsBox, st, c);
+                        const size_t sb = stack_lds(v);
+                        const size_t total = sb ? ((lds + 15u) & ~(size_t)15u) + sb : lds;
+                        const hipError_t e = trace_occupancy(&d->occupancy(v), v, total);
+                        if (e != hipSuccess) return e;
+                        bool ok = false;
+                        if (keeps_workgroups(v, total, ok) != hipSuccess) (void)hipGetLastError();
+                        fits = fits && ok;
+                    }
+                return hipSuccess;
+            };
+            bool fits = false;
+            HIP_TRY(occupancy_lds(fits));
+            if (!fits && wide) {
+                wide = false;
+                tri = trace_mesh_kind(w.packed.ntri > 0, !w.tbvh.nodes.empty());
+                HIP_TRY(occupancy_global());
+                HIP_TRY(occupancy_lds(fits));
+                if (!fits) {
+                    // the tree itself does not fit: give up the LDS tree, not
+                    // the wide triangle walk (its stacks fit without the tree)
+                    wide = true;
+                    tri = 3;
+                    HIP_TRY(occupancy_global());
+                }
+            }
+            if (fits) d->lds_bytes = lds;
+        }
+    }
+    const uint64_t bpc = env_u64("RT_AMD_BLOCKS_PER_CU", 0);
+    for (int c = 0; c < 3; ++c)
+        for (int st = 0; st < 2; ++st) {
+            if (bpc)
+                for (int search : {kSearchBrute, kSearchGlobal, kSearchLdsBox})
+                    d->blocks_per_cu[search][c][st] = (int)bpc;
+            for (int search : {kSearchBrute, kSearchGlobal})
+                d->blocks_per_cu[search][c][st] = std::max(d->blocks_per_cu[search][c][st], 1);
+        }
+    if (wide && !w.tbvh.nodes.empty()) d->tw_depth = tw_depth;
+    return 0;
+}
+
+int device_for(WorldState &w, int want, DeviceState *&out) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        set_error("no HIP device available: the MI355X render path requires a GPU");
+        return -3;
+    }
+    int dev = want;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    if (dev >= count) {
+        set_error("device ordinal out of range");
+        return -1;
+    }
+    HIP_TRY(hipSetDevice(dev));
+    auto &slot = w.devices[dev];
+    if (!slot) {
+        auto d = std::make_unique<DeviceState>();
+        d->device = dev;
+        int rc = create_stream_and_events(d.get());
+        if (rc) return rc;
+        // LDS trees above 64 KB per workgroup need the kernels' opt-in, before
+        // any occupancy query or launch; a runtime that refuses it keeps the
+        // 64 KB cap (RtRenderStats::sphere_tree reports what a frame walked)
+        size_t lds_cap = kLdsPerCu;
+        if (trace_lds_opt_in() != hipSuccess) {
+            (void)hipGetLastError();
+            lds_cap = kLdsDefaultMax;
+        }
+        lds_cap = std::min<size_t>(lds_cap, env_u64("RT_AMD_LDS_MAX", kLdsPerCu));
+        rc = upload_scene(w, d.get());
+        if (rc) return rc;
+        rc = choose_lds_layout(w, d.get(), lds_cap);
+        if (rc) return rc;
+        rc = upload_triangle_trees(w, d.get());
+        if (rc) return rc;
+        HIP_TRY(d->counter.grow(2 * kMaxParts * 32));
+        slot = std::move(d);
+    }
+    out = slot.get();
+    return 0;
+}
+
+}  // namespace rtamd

@@ -10,7 +10,7 @@
 namespace rtamd {
 
 enum : uint32_t { kRngCounter = 1, kRngReplay = 2 };
-// SERIAL-mode passes (runtime.cpp render_frame_serial), kernel-internal modes:
+// SERIAL-mode passes (serial_states.cpp render_frame_serial), kernel-internal modes:
 // jobs are (sample, variant) pairs and store the sample's diffuse/metal scatter
 // count b (the reference draws 2 + 3b numbers per sample) instead of a colour.
 //   kRngSerialCount: variant k = candidate; start state win[2 jl + 3 (lo[jl] + k)]

@@ -1667,7 +1667,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner, A
                     const bool cam = kMesh == 2 && bounce == 0 && p.cam_nnodes != 0;
                     if (tri_begin(p, org, dir, best_t, cam, e, tri_t, tri_i, tri_in, tri_done)) {
                         // (the lists index the camera-origin records, which exist
-                        // without the camera tree's nodes: runtime.cpp prepare_camera)
+                        // without the camera tree's nodes: primary_lists.cpp prepare_camera)
                         if (kAdapt && bounce == 0 && p.ptl_off != nullptr) {
                             tri_primary_list_adapt(p, xtail().list, lane_job(slot), org, dir, best_t, tri_t, tri_i,
                                                    tri_in, tri_done);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <future>
 #include <map>
 #include <mutex>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "device_buffer.h"
 #include "render.h"
 #include "scene.h"
 
@@ -36,94 +38,119 @@ const std::string &last_error();
 // One device's copy of a scene plus the scratch a frame needs.  Buffers grow
 // on demand and persist across frames (the interactive flow re-renders the
 // same scene with a moved camera, GameView.swift:198-219 / lib.rs:60-63).
+// Every buffer owns its memory (device_buffer.h): the destructor selects the
+// device and destroys the events and the stream, the buffers follow as members.
 struct DeviceState {
     int device = -1;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t sev[3] = {nullptr, nullptr, nullptr};  // SERIAL mode: start, tables done, states found
-    float4 *sph_hot = nullptr, *sph_cold = nullptr, *tri_hot = nullptr, *tri_geo = nullptr;
-    float *mats = nullptr;
-    float4 *sph_shade = nullptr;
-    uint32_t *sph_kind = nullptr;
+    DevBuf<float4> sph_hot, sph_cold, tri_hot, tri_geo;
+    DevBuf<float> mats;
+    DevBuf<float4> sph_shade;
+    DevBuf<uint32_t> sph_kind;
     uint32_t nsph = 0, nsph_padded = 0, ntri = 0;
-    float4 *bvh_nodes = nullptr, *bvh_prims = nullptr, *big_hot = nullptr;
-    uint32_t *bvh_miss = nullptr, *bvh_prim_id = nullptr, *big_id = nullptr;
-    uint16_t *bvh_miss16 = nullptr;
+    DevBuf<float4> bvh_nodes, bvh_prims, big_hot;
+    DevBuf<uint32_t> bvh_miss, bvh_prim_id, big_id;
+    DevBuf<uint16_t> bvh_miss16;                                // (null: no LDS box tree)
     uint32_t nnodes = 0, nbig = 0, nprims = 0;
-    uint4 *tbvh_nodes = nullptr;                                // triangle BVH (bvh.h qnodes)
-    float4 *tbvh_tris = nullptr;
-    uint32_t *tbvh_loose = nullptr;
+    DevBuf<uint4> tbvh_nodes;                                   // triangle BVH (bvh.h qnodes)
+    DevBuf<float4> tbvh_tris;
+    DevBuf<uint32_t> tbvh_loose;
     uint32_t tnodes = 0, ttris = 0, tloose = 0;
-    uint4 *tw_nodes = nullptr;                                  // its 4-wide image (bvh.h wnodes)
+    DevBuf<uint4> tw_nodes;                                     // its 4-wide image (bvh.h wnodes); null: binary walk
     uint32_t tw_depth = 0;                                      // stack entries per lane
-    float *tw_tris = nullptr;                                   // per-cell trees' records (tcells)
-    uint4 *cam_nodes = nullptr;                                 // camera-origin triangle BVH
-    float4 *cam_tris = nullptr;
+    DevBuf<float> tw_tris;                                      // per-cell trees' records (tcells); null: none
+    DevBuf<uint4> cam_nodes;                                    // camera-origin triangle BVH (null: records only)
+    DevBuf<float4> cam_tris;                                    // (null: no camera records)
     uint32_t cam_nnodes = 0;
     uint64_t cam_version = 0;                                  // WorldState::ctree_version uploaded
-    uint32_t *ptl_off = nullptr, *ptl_items = nullptr;         // primary-ray triangle lists
+    DevBuf<uint32_t> ptl_off, ptl_items;                        // primary-ray triangle lists (ptl_off null: none)
     uint64_t ptl_version = 0;
-    uint2 *spl = nullptr;                                       // primary sphere lists
+    DevBuf<uint2> spl;                                          // primary sphere lists (null: every ray walks)
     uint64_t spl_version = 0;
     // primary sphere lists built on the device (serial.hip launch_sphere_lists)
-    uint2 *gspl = nullptr;           size_t gspl_cap = 0;
-    int4 *gspl_rects = nullptr;      size_t gspl_rects_cap = 0;
-    uint32_t *gspl_flag = nullptr;   size_t gspl_flag_cap = 0;
-    CameraModel gspl_cam{};
-    size_t gspl_w = 0, gspl_h = 0;
-    bool gspl_built = false, gspl_ok = false;
-    // primary triangle strip lists built on the device (tri_lists.hip): the
-    // records' boxes (uploaded once per ctree_version), the lists, scratch
-    float *gptl_box = nullptr;       size_t gptl_box_cap = 0;
-    uint64_t gptl_box_version = 0;                             // WorldState::ctree_version uploaded
-    uint32_t *gptl_off = nullptr;    size_t gptl_off_cap = 0;
-    uint32_t *gptl_items = nullptr;  size_t gptl_items_cap = 0;
-    int4 *gptl_rects = nullptr;      size_t gptl_rects_cap = 0;
-    uint32_t *gptl_count = nullptr;  size_t gptl_count_cap = 0;
-    uint32_t *gptl_alw = nullptr;    size_t gptl_alw_cap = 0;
-    uint32_t *gptl_meta = nullptr;   size_t gptl_meta_cap = 0;
-    uint32_t *gptl_hmeta = nullptr;                            // (pinned: the lengths read back)
-    CameraModel gptl_cam{};
-    size_t gptl_w = 0, gptl_h = 0;
-    uint64_t gptl_ctree = 0;
-    uint32_t gptl_spr = 0, gptl_total = 0, gptl_nalways = 0;
-    bool gptl_built = false, gptl_ok = false, gptl_host = false;  // gptl_host: out of range, the host builds
+    // for (cam, w, h); ok = false: no lists (every primary ray walks)
+    struct DeviceSphereLists {
+        DevBuf<uint2> lists;
+        DevBuf<int4> rects;
+        DevBuf<uint32_t> flag;
+        CameraModel cam{};
+        size_t w = 0, h = 0;
+        bool built = false, ok = false;
+        bool current(const CameraModel &c, size_t width, size_t height) const {
+            return built && w == width && h == height && std::memcmp(&cam, &c, sizeof(c)) == 0;
+        }
+        void remember(const CameraModel &c, size_t width, size_t height) {
+            cam = c;
+            w = width;
+            h = height;
+            built = true;
+        }
+    } gspl;
+    // primary triangle strip lists built on the device (tri_lists.hip) for
+    // (cam, w, h, ctree): the records' boxes (uploaded once per
+    // ctree_version), the lists, scratch
+    struct DeviceTriLists {
+        DevBuf<float> box;
+        uint64_t box_version = 0;                              // WorldState::ctree_version uploaded
+        DevBuf<uint32_t> off, items;
+        DevBuf<int4> rects;
+        DevBuf<uint32_t> count, alw, meta;
+        PinnedBuf<uint32_t> hmeta;                             // (the lengths read back)
+        CameraModel cam{};
+        size_t w = 0, h = 0;
+        uint64_t ctree = 0;
+        uint32_t spr = 0, total = 0, nalways = 0;
+        bool built = false, ok = false, host = false;          // host: out of range, the host builds
+        bool current(const CameraModel &c, size_t width, size_t height, uint64_t ctree_version) const {
+            return built && w == width && h == height && ctree == ctree_version &&
+                   std::memcmp(&cam, &c, sizeof(c)) == 0;
+        }
+        void remember(const CameraModel &c, size_t width, size_t height, uint64_t ctree_version) {
+            cam = c;
+            w = width;
+            h = height;
+            ctree = ctree_version;
+            built = true;
+        }
+    } gptl;
     int last_ptl = 0;                                          // rt_primary_tri_lists of the last launch
     size_t lds_bytes = 0;                                      // 0: tree not LDS-stageable
     // corner records (bvh.h SphereBVH::corner), uploaded when the sphere-only
     // frame kernels can stage them without losing a workgroup per CU
-    uint4 *bvh_corner = nullptr;
+    DevBuf<uint4> bvh_corner;                                   // (null: none uploaded)
     size_t corner_bytes = 0;                                   // 0: box records (or no LDS tree)
-    float *samples = nullptr;        size_t samples_cap = 0;   // sample slab (3 planes)
-    float *ring = nullptr;           size_t ring_cap = 0;      // per-wave sample rings (fused resolve)
-    uint32_t *out = nullptr;         size_t out_cap = 0;       // RGBA8 tile (host path)
-    uint32_t *tile = nullptr;        size_t tile_cap = 0;      // multi-device: this rank's tile
-    uint32_t *gath = nullptr;        size_t gath_cap = 0;      // multi-device root: gathered tiles
+    DevBuf<float> samples;                                      // sample slab (3 planes)
+    DevBuf<float> ring;                                         // per-wave sample rings (fused resolve)
+    DevBuf<uint32_t> out;                                       // RGBA8 tile (host path)
+    DevBuf<uint32_t> tile;                                      // multi-device: this rank's tile
+    DevBuf<uint32_t> gath;                                      // multi-device root: gathered tiles
     hipEvent_t done = nullptr;       // end of the last frame enqueued on this device ...
     hipStream_t done_stream = nullptr;  // ... and the stream it was enqueued on
-    uint32_t *replay = nullptr;      size_t replay_cap = 0;
+    DevBuf<uint32_t> replay;
     // SERIAL mode (render_frame_serial): start states, candidate offsets, the
     // stream window of a chunk, xorshift jump matrices, control block
-    uint32_t *sstates = nullptr;     size_t sstates_cap = 0;
-    double *stab = nullptr;          size_t stab_cap = 0;   // prediction tables (render.h serial_tab_doubles)
-    double *sscan = nullptr;         size_t sscan_cap = 0;  // their scan's scratch
-    uint32_t *slo = nullptr;         size_t slo_cap = 0;    // an iteration's window bases (launch_serial_window)
-    uint32_t *ssbend = nullptr;      size_t ssbend_cap = 0; // superblock ends and block starts (launch_serial_walk)
-    uint32_t *ssb = nullptr;         size_t ssb_cap = 0;
-    uint32_t *swin = nullptr;        size_t swin_cap = 0;
-    uint32_t *sbend = nullptr;       size_t sbend_cap = 0;
-    uint32_t *spath = nullptr;       size_t spath_cap = 0;  // block walks' paths (L x K)
-    float *sptab = nullptr;          size_t sptab_cap = 0;  // pixel table pass: b per (pixel, position)
-    uint4 *sspix = nullptr;          size_t sspix_cap = 0;  // pixel table pass: spans per pixel, 2 buffers
-    float *sptab2 = nullptr;         size_t sptab2_cap = 0; // (the previous iteration's table: reuse)
-    uint32_t *sfin = nullptr;                               // chain result (4 + kMaxWalkBlocks)
-    uint32_t *sjump = nullptr;
-    uint32_t *sctrl = nullptr;
-    unsigned long long *scheck = nullptr;                       // chain-check count
-    uint32_t *counter = nullptr;                                // job counters: 2 sets of kMaxParts
+    DevBuf<uint32_t> sstates;
+    DevBuf<double> stab;                                        // prediction tables (render.h serial_tab_doubles)
+    DevBuf<double> sscan;                                       // their scan's scratch
+    DevBuf<uint32_t> slo;                                       // an iteration's window bases (launch_serial_window)
+    DevBuf<uint32_t> ssbend;                                    // superblock ends and block starts (launch_serial_walk)
+    DevBuf<uint32_t> ssb;
+    DevBuf<uint32_t> swin;
+    DevBuf<uint32_t> sbend;
+    DevBuf<uint32_t> spath;                                     // block walks' paths (L x K)
+    DevBuf<float> sptab;                                        // pixel table pass: b per (pixel, position)
+    DevBuf<uint4> sspix;                                        // pixel table pass: spans per pixel, 2 buffers
+    DevBuf<float> sptab2;                                       // (the previous iteration's table: reuse)
+    DevBuf<uint32_t> sfin;                                      // chain result (4 + kMaxWalkBlocks)
+    DevBuf<uint32_t> sjump;
+    DevBuf<uint32_t> sctrl;
+    DevBuf<unsigned long long> scheck;                          // chain-check count
+    DevBuf<uint32_t> counter;                                   // job counters: 2 sets of kMaxParts
     uint32_t cset = 0;              // the set the next frame launch uses ...
     bool cset_clean[2] = {false, false};  // ... and whether each set is known to be zero
-    unsigned long long *stats = nullptr; size_t stats_cap = 0;  // per-wave counter records
+    DevBuf<unsigned long long> stats;                           // per-wave counter records
     // resident workgroups per CU of the scene's kernel instances (render.h
     // TraceVariant), [search][kind][step], queried once at device setup for the
     // scene's family (the corner search: frame kinds only)
@@ -146,7 +173,7 @@ struct DeviceState {
     // render_frame(..., defer_stats) the host collects them later
     // (collect_frame_stats), so several devices' counted frames run at once
     std::vector<hipEvent_t> tev;
-    unsigned long long *hrec = nullptr; size_t hrec_cap = 0;
+    PinnedBuf<unsigned long long> hrec;
     struct PendingStats {
         bool active = false;
         size_t nrec = 0;          // records (waves x kStatSlots) in hrec
@@ -215,27 +242,28 @@ struct AccumState {
     uint32_t held = 0;            // N: samples per pixel in the sums
     float cam[12] = {};           // the camera they were traced with ...
     uint64_t edit_version = 0;    // ... and the scene version
-    float *sums = nullptr;        // 3 planes of width * height (R, G, B), top row first
-    uint32_t *replay = nullptr;   // REPLAY: width * height * stride start states
+    DevBuf<float> sums;           // 3 planes of width * height (R, G, B), top row first
+    DevBuf<uint32_t> replay;      // REPLAY: width * height * stride start states
     hipEvent_t done = nullptr;    // end of the last pass ...
     hipStream_t done_stream = nullptr;  // ... and the stream it ran on (nullptr: none yet)
     // Adaptive accumulation (rt_adapt_enable): the pixels still
     // sampled are those of list[cur] (frame indices, ascending), nactive of
     // them, all holding `held` samples; the others stopped at count[pixel].
-    // Everything below is allocated by adapt_enable and freed with the sums.
+    // Everything below is allocated by adapt_enable and freed with the sums
+    // (frame last: its presence means all are).
     bool adaptive = false;
     float tolerance = 0.0f, bias = 0.0f;
     uint32_t min_samples = 0;
-    float *sumsq = nullptr;       // width * height: the fold of y y, y = (r + g) + b
-    uint32_t *count = nullptr;    // width * height: samples each pixel holds
-    uint32_t *frame = nullptr;    // width * height RGBA8: frozen pixels keep their last pass's bytes
-    uint32_t *list[2] = {nullptr, nullptr};  // two lists alternate (the compaction's input and output)
+    DevBuf<float> sumsq;          // width * height: the fold of y y, y = (r + g) + b
+    DevBuf<uint32_t> count;       // width * height: samples each pixel holds
+    DevBuf<uint32_t> frame;       // width * height RGBA8: frozen pixels keep their last pass's bytes
+    DevBuf<uint32_t> list[2];     // two lists alternate (the compaction's input and output)
     uint32_t cur = 0;
     uint32_t nactive = 0;         // entries of list[cur] (meaningful while held != 0)
-    uint32_t *keep = nullptr;     // width * height flags of the last decision
-    uint32_t *totals = nullptr;   // the compaction's block totals
-    uint32_t *d_len = nullptr;    // the new list length on the device ...
-    uint32_t *h_len = nullptr;    // ... and in pinned host memory
+    DevBuf<uint32_t> keep;        // width * height flags of the last decision
+    DevBuf<uint32_t> totals;      // the compaction's block totals
+    DevBuf<uint32_t> d_len;       // the new list length on the device ...
+    PinnedBuf<uint32_t> h_len;    // ... and in pinned host memory
 };
 
 // One pass of an accumulation, for render_frame: n0 samples held, the frame's

@@ -1,0 +1,74 @@
+// runtime_internal.h -- what the host runtime's units share with each other
+// (device_state, primary_lists, frame, serial_states, multi, accum) and with
+// nobody else: runtime.h is the interface the C ABI sees.
+#pragma once
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include <rccl/rccl.h>
+
+#include "../../include/raytracer_amd.h"
+#include "runtime.h"
+
+namespace rtamd {
+
+#define HIP_TRY(expr)                                                                 \
+    do {                                                                              \
+        hipError_t e_ = (expr);                                                       \
+        if (e_ != hipSuccess) {                                                       \
+            set_error(std::string(#expr) + " failed: " + hipGetErrorString(e_));      \
+            return -2;                                                                \
+        }                                                                             \
+    } while (0)
+
+#define NCCL_TRY(expr)                                                                \
+    do {                                                                              \
+        ncclResult_t r_ = (expr);                                                     \
+        if (r_ != ncclSuccess) {                                                      \
+            set_error(std::string(#expr) + " failed: " + ncclGetErrorString(r_));     \
+            return -4;                                                                \
+        }                                                                             \
+    } while (0)
+
+// (read at every use: tests and tools change the environment between frames)
+inline uint64_t env_u64(const char *name, uint64_t dflt) {
+    const char *v = std::getenv(name);
+    if (!v || !*v) return dflt;
+    return std::strtoull(v, nullptr, 10);
+}
+
+inline bool same_cam(const CameraModel &a, const CameraModel &b) {
+    return std::memcmp(&a, &b, sizeof(a)) == 0;
+}
+
+static_assert(kPrimaryTriStripW == kTriStripW, "render.h and bvh.h strip widths");
+static constexpr uint64_t kMaxParts = kMaxJobParts;  // job-queue partitions (render.h)
+static constexpr uint32_t kPixtabParts = 64;  // the pixel table pass's (zeroed by the window kernel)
+
+// device_state.cpp: w's state on device `want` (< 0: the current device),
+// created on first use -- stream and events, the scene upload, the LDS layout
+// and occupancy decisions.  Selects the device.
+int device_for(WorldState &w, int want, DeviceState *&out);
+
+// primary_lists.cpp
+bool gpu_lists();      // RT_AMD_GPU_LISTS
+bool gpu_tri_lists();  // RT_AMD_GPU_TRI_LISTS
+void prepare_camera_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height, bool lists);
+bool prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height);
+int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
+                        hipStream_t s, bool &ok);
+int device_tri_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
+                     hipStream_t s, bool &ok);
+
+// serial_states.cpp
+int serial_check_args(size_t width, size_t height, const RtRenderOptions &o);
+int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size_t height,
+                       const RtRenderOptions &o, DeviceState *d, hipStream_t s, RtRenderStats *stats);
+
+// multi.cpp: devices [first, first + n) (first < 0: from the current device), checked
+int device_list(int first, int n, std::vector<int> &devs);
+
+}  // namespace rtamd

@@ -18,7 +18,7 @@ namespace rtamd {
 // ------------------------------------------------------------ SERIAL mode
 // The reference draws every sample from ONE xorshift32 stream (common.rs:321):
 // sample j starts at stream position P_j = 2j + 3B_j, B_j = the diffuse/metal
-// scatters of all earlier samples.  runtime.cpp render_frame_serial finds
+// scatters of all earlier samples.  serial_states.cpp render_frame_serial finds
 // every P_j chunk by chunk: trace_kernel (kRngSerialCount) traces each sample
 // of the chunk from K candidate positions around its predicted one,
 // the walk kernels follow the true path through that table, and the frame
@@ -715,7 +715,7 @@ __global__ __launch_bounds__(256) void serial_scan_apply_kernel(double *__restri
 __global__ __launch_bounds__(256) void serial_reach_kernel(double *__restrict__ tab, uint32_t npix, uint32_t spp,
                                                            uint32_t L, uint32_t n0) {
     const SerialPred m{tab, tab + npix + 1, spp, npix};
-    const uint32_t N = npix * spp;  // (< 2^32, runtime.cpp)
+    const uint32_t N = npix * spp;  // (< 2^32, serial_states.cpp)
     const uint32_t q = max(1u, L / 4u);
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long *dmax = reinterpret_cast<unsigned long long *>(tab + 5 * (size_t)npix + 3);
@@ -1040,7 +1040,7 @@ hipError_t launch_sphere_lists(const float4 *prims, uint32_t n, const double *Mi
     return hipGetLastError();
 }
 
-// Multi-device frames (runtime.cpp render_frame_multi): rank g's tile holds
+// Multi-device frames (multi.cpp render_frame_multi): rank g's tile holds
 // the image rows of its row blocks (tile row k = image row tile_row(k)); the
 // root's gather buffer holds nranks tiles of max_rows rows each.  One thread
 // per RGBA8 word of the frame reads its word from its rank's tile: the frame

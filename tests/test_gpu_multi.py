@@ -213,7 +213,7 @@ def test_serial_multi_device_path_one_device():
 
 
 def test_job_counter_sets_across_streams_serial_and_partitions(monkeypatch):
-    """The double-buffered job counters (runtime.cpp: a frame launch takes one
+    """The double-buffered job counters (frame.cpp: a frame launch takes one
     set, zeroed by the launch before it, and zeroes the other): COUNTER frames
     on a user stream and on the library stream, a SERIAL frame (whose passes
     reset the sets) between them, and the partition count changed from frame

@@ -6,7 +6,7 @@ The library traces the next samples from candidate stream positions (every
 candidate: the count pass; or each block's distinct live offsets: the
 coalescing search), follows the true path as far as it stays inside the
 candidate windows, repeats from there, and renders from the start states it
-found (runtime.cpp render_frame_serial).  Cases: the
+found (serial_states.cpp render_frame_serial).  Cases: the
 examples/c_raytracer.rs frame (200x200, 16 spp, depth 8 -- render()'s
 settings, lib.rs:51), BASELINE configs[0] (C1), the sphere BVH (RTOW) and the
 triangle trees, edge frames, row tiles, a non-default seed, and windows forced
@@ -158,7 +158,7 @@ def test_serial_table_reuse_after_stops(monkeypatch):
 
 
 SEARCHES = {
-    # runtime.cpp serial_find_states: the pixel table (default from 4 spp), the
+    # serial_states.cpp serial_find_states: the pixel table (default from 4 spp), the
     # count pass + block walks, the coalescing block search
     "pixtab": dict(RT_AMD_SERIAL_PIXTAB="1"),
     # the pixel table's block walks and state gather reading the table in
