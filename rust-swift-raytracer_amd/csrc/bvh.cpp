@@ -617,7 +617,7 @@ void build_wide_image(TriangleBVH &tb) {
             }
             for (int k = 0; k < 3; ++k) r[6 * c + k] = word(s[c], k);
             // the normal box as halves, rounded outward from the float box
-            // (render.hip tri_wide_child decodes them with v_cvt_f32_f16)
+            // (tri_search.h tri_wide_child decodes them with v_cvt_f32_f16)
             const float *nf = &tb.nodes[(size_t)s[c] * 16];
             uint16_t h[6];
             for (int k = 0; k < 3; ++k) {
@@ -829,7 +829,7 @@ CameraTriangleBVH build_camera_triangle_bvh(const std::vector<Triangle> &tris,
     const double o[3] = {origin[0], origin[1], origin[2]};
     const double onorm = std::fabs(o[0]) + std::fabs(o[1]) + std::fabs(o[2]);
     if (!(onorm < 1e18)) return out;  // the kernel brute-forces such origins
-    // the kernel's per-ray margin (render.hip triangles_bvh) for this origin
+    // the kernel's per-ray margin (tri_search.h tri_begin) for this origin
     double dist = tb.radius + 2 * onorm;
     for (int k = 0; k < 3; ++k) dist += std::fabs(o[k] - tb.centre[k]);
     const double rho = 1e-5 * (dist + onorm + tb.mag) * (1 + 1e-6);
@@ -1071,7 +1071,7 @@ PrimarySphereLists build_primary_sphere_lists(const SphereBVH &bv, const CameraM
         const double r = std::sqrt((double)s[3]) * (1 + 1e-6);
         const double a = std::sqrt((c[0] - o[0]) * (c[0] - o[0]) + (c[1] - o[1]) * (c[1] - o[1]) +
                                    (c[2] - o[2]) * (c[2] - o[2]));
-        // the walk's margin (render.hip sph_inflation, K = 3e-3), doubled
+        // the walk's margin (sphere_search.h sph_inflation, K = 3e-3), doubled
         const double R = r + 2 * 3e-3 * (a + r) * 1.01 + 2 * e_abs;
         if (!std::isfinite(R) || !std::isfinite(a)) return PrimarySphereLists{};
         double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;

@@ -37,7 +37,7 @@ struct SphereBVH {
     float centre[3] = {0, 0, 0};
     float radius = 0, rmax = 0, mag = 0, inv_rmin = 0;
     uint32_t depth = 0;
-    // Corner records (render.hip stage_tree copies them to LDS verbatim): 32 u32
+    // Corner records (sphere_search.h stage_tree copies them to LDS verbatim): 32 u32
     // per node, 8 slots of 4, one per ray-direction octant o (bit k set: the
     // direction is negative on axis k).  Slot o = the box's near corner for o
     // (per axis lo where the direction is positive, hi where it is negative;
@@ -91,7 +91,7 @@ struct TriangleBVH {
     std::vector<uint32_t> qnodes;
     QuantGrid qbox;
     float nbase = -1, nstep = 1;    // normal grid (all three axes)
-    // 4-wide image of the same tree (render.hip tri_wide): one 128-B record per
+    // 4-wide image of the same tree (tri_search.h tri_wide_child): one 128-B record per
     // wide node, 32 u32: child c's box words (qnodes words 0-2 of the binary
     // node it is) at 6c..6c+2, its normal box at 6c+3..6c+5 as six halves
     // (lo.xyz, hi.xyz, rounded outward from the float normal box), child words

@@ -399,7 +399,7 @@ hipError_t launch_serial_pixtab_gather(const uint32_t *ctrl, const float *ptab, 
 inline uint64_t serial_pixtab_emax64(uint64_t spp, uint64_t K, uint64_t depth) {
     return 2u * (spp - 1u) + 3u * (depth * (spp - 1u) + K) + 1u;
 }
-// Coalescing block search (render.hip serial_coalesce_kernel): one workgroup
+// Coalescing block search (serial_coalesce.h serial_coalesce_kernel): one workgroup
 // per block of R samples of the iteration writes bend and path (layouts of
 // launch_serial_walk's block walks) by tracing each block's distinct live
 // offsets once per sample, from win and lo (p.win, p.slo, p.ctrl set as for a
@@ -465,7 +465,7 @@ hipError_t launch_assemble(const uint32_t *gathered, uint32_t *out, uint32_t wid
 // (hipErrorInvalidValue: no such instance)
 hipError_t trace_occupancy(int *blocks_per_cu, TraceVariant v, size_t lds_bytes);
 size_t trace_lds_bytes(const TraceParams &p, bool corner = false);
-// the sphere tree's LDS copy (render.hip stage_tree)
+// the sphere tree's LDS copy (sphere_search.h stage_tree)
 __host__ __device__ inline size_t trace_tree_lds(uint32_t nnodes, uint32_t nprims, uint32_t nsph_padded) {
     return (size_t)nnodes * 64 + (size_t)nprims * 20 + (size_t)nsph_padded * 36;
 }

@@ -3,7 +3,7 @@
 // states; the estimate reduction and its scans; reach, check count, table reuse
 // and gather), the primary sphere lists built on the device, and the
 // multi-device frame assembly.  The kernels that trace (trace_kernel,
-// serial_coalesce_kernel) are in render.hip.
+// serial_coalesce_kernel) are in render.hip's unit (serial_coalesce.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

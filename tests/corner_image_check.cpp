@@ -15,7 +15,7 @@
 // components exactly +0 or -0, components below 1e-20, origins inside leaf
 // boxes), each with an infinite and a finite best t and with the full and the
 // smallest inflation: a host emulation of the kernel's corner step
-// (render.hip sphere_node_corner) visits the same nodes in the same order,
+// (sphere_search.h sphere_node_corner) visits the same nodes in the same order,
 // takes the same skip decisions and enters the same leaves as an emulation of
 // the box step (sphere_node, LDS form).  float arithmetic, fmaf, slab_rcp's
 // clamp; both emulations share the reciprocal.
@@ -57,7 +57,7 @@ struct Rng {  // xorshift64*
     uint32_t below(uint32_t n) { return (uint32_t)(next() >> 33) % n; }
 };
 
-static float slab_rcp(float d) {  // render.hip: med3(rcp(d), -1e20, 1e20)
+static float slab_rcp(float d) {  // sphere_search.h: med3(rcp(d), -1e20, 1e20)
     const float r = 1.0f / d;
     return r < -1e20f ? -1e20f : r > 1e20f ? 1e20f : r;
 }
@@ -66,7 +66,7 @@ struct Step { uint32_t node; bool skip; uint32_t leaf; };  // leaf: entered leaf
 
 struct Ray { float o[3], d[3]; };
 
-// the walk's per-ray inputs (render.hip sph_bound / sph_inflation)
+// the walk's per-ray inputs (sphere_search.h sph_bound / sph_inflation)
 static float inflation(const SphereBVH &bv, const Ray &r, float best_t, bool full) {
     const float e_abs = 2e-6f * ((std::fabs(r.o[0]) + std::fabs(r.o[1])) + std::fabs(r.o[2]) + bv.mag);
     if (!full) return e_abs;

@@ -1,5 +1,5 @@
 """The LDS sphere tree as octant corner records (bvh.h SphereBVH::corner,
-render.hip sphere_node_corner): sphere-only frame kernels walk them when the
+sphere_search.h sphere_node_corner): sphere-only frame kernels walk them when the
 image fits a workgroup's LDS share, everything else keeps the box records.
 The layout changes work per node, never a sample: every comparison is
 bit-exact, and the BVH counters equal the box records' (the same nodes in the

@@ -1,4 +1,4 @@
-"""Deferred leaf tests in the lean corner walk (render.hip trace_body kDefer,
+"""Deferred leaf tests in the lean corner walk (trace_body.h trace_body kDefer,
 DESIGN.md 5.2): a lane that enters a leaf records it and walks on, and the wave
 tests the recorded leaves in shared passes.  Deferral only delays the decrease
 of best_t, so the tested leaves are a superset of the immediate walk's and the

@@ -1,4 +1,4 @@
-"""Where the frame kernels derive and keep their per-lane state (render.hip
+"""Where the frame kernels derive and keep their per-lane state (trace_body.h
 trace_body): the sphere walk's reciprocals, octant and entry node are derived
 at the walk (sphere-only, unsliced kernels), a leaf's second sphere is read
 with its first (LDS trees), the scattered and the new primary directions share

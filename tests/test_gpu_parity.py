@@ -436,7 +436,7 @@ def test_primary_sphere_lists_follow_camera_and_size(monkeypatch, gpu):
     (dict(seed=73, n=800, spread=30.0, radius=0.02, big=False, cam=(0.0, 0.0, 20.0)), 97, 61),
 ])
 def test_device_sphere_lists_many_spheres(monkeypatch, case, w, h):
-    """The device list build (render.hip spl_fill_kernel: tiles, spheres culled
+    """The device list build (serial.hip spl_fill_kernel: tiles, spheres culled
     256 at a time, early exit when a tile has overflowed) equals the host build
     list for list on scenes with thousands of spheres, and the frame equals
     brute force."""

@@ -4,9 +4,9 @@ Compiles render.hip for gfx950 to assembly with line tables (-g changes no
 code: the instruction count is checked against the plain build), then counts
 the instructions of one kernel by class (VALU, SALU, vector memory, LDS,
 scalar memory, branches, waits) and by the source region of their innermost
-location: the helper functions of render.hip and the sections of the
-trace_kernel loop (ray setup, sphere walk, triangle walk, shading, sample
-store, fused resolve, refill, direction normalisation).  Static counts weigh
+location: the functions of render.hip and of the headers it includes, keyed
+on (file, line), and the sections of trace_body (trace_body.h) between its
+RT_STAMP lines.  Static counts weigh
 every instruction once; tools/stamps.py gives the dynamic (cycle) shares.
 
   python tools/isa_breakdown.py [--kernel 1,1,0,0,0,0] [--defs "-DX"] [--asm file.s]
@@ -20,7 +20,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "rust-swift-raytracer_amd", "csrc", "render.hip")
+CSRC = os.path.join(ROOT, "rust-swift-raytracer_amd", "csrc")
+SRC = os.path.join(CSRC, "render.hip")
+TRACE_BODY = os.path.join(CSRC, "trace_body.h")
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--offload-arch=gfx950",
          "--cuda-device-only", "-S"]
 
@@ -70,46 +72,55 @@ def klass(op):
     return "other"
 
 
-def regions():
-    """(first line, last line, name) of render.hip's functions and loop sections."""
-    src = open(SRC).read().split("\n")
-    out = []
-    head = re.compile(r"^(?:__device__|__global__|static|RT_HOST_DEVICE|void|hipError_t|uint32_t|size_t)\b")
-    skip = {"__launch_bounds__", "amdgpu_waves_per_eu", "__attribute__", "if", "for"}
-    starts = []
-    for i, l in enumerate(src, 1):
-        if not head.match(l) or l.rstrip().endswith(";"):
+def unit_files():
+    """render.hip and the headers of csrc/ it includes, directly or not."""
+    seen, todo = [], [SRC]
+    while todo:
+        f = todo.pop()
+        if f in seen or not os.path.exists(f):
             continue
-        names = [n for n in re.findall(r"(\w+)\s*\(", l) if n not in skip]
-        if names:
-            starts.append((i, names[0]))
-    for k, (i, name) in enumerate(starts):
-        end = starts[k + 1][0] - 1 if k + 1 < len(starts) else len(src)
-        out.append((i, end, name))
-    # sections of trace_kernel's loop, by the comments that open them
-    marks = [("---- ray_color's bounce loop", "loop: ray setup"),
-             ("kStep: at most p.steps node visits", "loop: sphere walk"),
-             ("if (phase == kTriInit)", "loop: triangle walk"),
-             ("if (phase == kShade)", "loop: shading"),
-             ("if (done) {", "loop: sample store (+ SERIAL counts)"),
-             ("---- fused resolve, at refill points", "loop: fused resolve"),
-             ("---- refill lanes whose path ended", "loop: refill"),
-             ("if (renorm) dir = unit(vdir);", "loop: direction normalisation"),
-             ("---- per-wave statistics", "after the loop")]
-    tk = next((a, b) for a, b, n in out if n == "trace_kernel")
-    pos = []
-    for text, name in marks:
-        for i in range(tk[0], tk[1] + 1):
-            if text in src[i - 1]:
-                pos.append((i, name))
-                break
-    pos.sort()
-    sec = []
-    for k, (i, name) in enumerate(pos):
-        end = pos[k + 1][0] - 1 if k + 1 < len(pos) else tk[1]
-        sec.append((i, end, name))
-    pre = (tk[0], pos[0][0] - 1, "kernel entry (LDS staging)") if pos else None
-    return out, ([pre] if pre else []) + sec
+        seen.append(f)
+        for inc in re.findall(r'^#include "([^"]+)"', open(f).read(), re.M):
+            todo.append(os.path.join(CSRC, inc))
+    return seen
+
+
+def regions():
+    """{file name: [(first line, last line, function name)]} of the unit's functions."""
+    head = re.compile(r"^(?:\s*(?:static\s+)?(?:__device__|__global__|__host__)|(?:static\s+)?"
+                      r"(?:void|hipError_t|uint32_t|size_t|int))\b")
+    skip = {"__launch_bounds__", "amdgpu_waves_per_eu", "__attribute__", "if", "for", "while", "trace_threads",
+            "trace_waves_per_eu"}
+    out = {}
+    for f in unit_files():
+        src = open(f).read().split("\n")
+        starts = []
+        for i, l in enumerate(src, 1):
+            if not head.match(l) or l.rstrip().endswith(";"):
+                continue
+            names = [n for n in re.findall(r"(\w+)\s*\(", l) if n not in skip]
+            if names:
+                starts.append((i, names[0]))
+        out[os.path.basename(f)] = [(i, starts[k + 1][0] - 1 if k + 1 < len(starts) else len(src), name)
+                                    for k, (i, name) in enumerate(starts)]
+    # trace_body is still one function: its sections are what lies between its
+    # RT_STAMP(k) lines (the segments tools/stamps.py times), which are code
+    name = {1: "ray setup", 2: "walks", 3: "shading", 4: "sample store", 5: "fused resolve", 6: "refill",
+            0: "direction normalisation"}
+    body = os.path.basename(TRACE_BODY)
+    src = open(TRACE_BODY).read().split("\n")
+    a, b = next((a, b) for a, b, n in out[body] if n == "trace_body")
+    stamps = [(i, int(m.group(1))) for i in range(a, b + 1)
+              for m in [re.match(r"\s*RT_STAMP\((\d)\);", src[i - 1])] if m]
+    loop = next(i for i in range(a, b + 1) if src[i - 1].strip() == "for (;;) {")
+    secs = [(a, loop - 1, "trace_body: entry (LDS staging)")]
+    prev = loop
+    for i, k in stamps:
+        secs.append((prev, i, "trace_body loop: " + name[k]))
+        prev = i + 1
+    secs.append((prev, b, "trace_body: after the loop"))
+    out[body] = [r for r in out[body] if r[2] != "trace_body"] + secs
+    return out
 
 
 def main():
@@ -130,19 +141,14 @@ def main():
         if l.lstrip().startswith(".file"):
             p = l.split()
             files[int(p[1])] = p[-3].strip('"') if p[-2] == "md5" else p[-1].strip('"')
-    funcs, secs = regions()
+    funcs = regions()
     by_class = collections.Counter(klass(op) for op, _ in body)
     by_region = collections.defaultdict(collections.Counter)
     for op, loc in body:
         name = "?"
         if loc is not None:
-            f = files.get(loc[0], "?")
-            if f.endswith("render.hip"):
-                line = loc[1]
-                name = next((n for a, b, n in secs if a <= line <= b), None) or \
-                    next((n for a, b, n in funcs if a <= line <= b), "render.hip")
-            else:
-                name = os.path.basename(f)
+            base = os.path.basename(files.get(loc[0], "?"))
+            name = next((f"{n} ({base})" for a, b, n in funcs.get(base, ()) if a <= loc[1] <= b), base)
             if loc[1] == 0:
                 name = "(no line)"
         by_region[name][klass(op)] += 1

@@ -231,7 +231,7 @@ static WaveCost wave_cost(const std::vector<std::vector<uint8_t>> &w, bool merge
     return r;
 }
 
-// SIM_WAVE_DEFER: deferred leaf tests (render.hip trace_body kDefer), a true
+// SIM_WAVE_DEFER: deferred leaf tests (trace_body.h trace_body kDefer), a true
 // lock-step run of 64 consecutive walks on their own geometry -- deferral
 // changes best_t and with it the cull decisions, so the recorded events do
 // not do.  A lane that enters a leaf records (leaf, t_near) and walks on, at
