@@ -318,6 +318,91 @@ int rt_adapt_read_sumsq(RtAccum *acc, float *sumsq);
  * may be NULL with cap 0), or a negative error. */
 long rt_adapt_read_active(RtAccum *acc, uint32_t *list, size_t cap);
 
+/* First-hit records: what the primary ray of each pixel hits.
+ *
+ * Maps pixels back to primitives, so that a viewer can pick ("this click is
+ * sphere 137", then rt_world_set_sphere_material), show debug views, and feed
+ * image-space steps with per-pixel primitive, depth and normal.
+ *
+ * For a width x height frame, the handle's camera (its 12 floats, as it is at
+ * the call) and sub-pixel offsets su, sv in [0, 1), the ray of the pixel at
+ * reference (row, col), row 0 = bottom, is the frame's primary ray with its
+ * two random draws replaced by the constants (common.rs:335-337):
+ *   u = (col as f32 + su) / (width  - 1) as f32     one rounded add, one
+ *   v = (row as f32 + sv) / (height - 1) as f32     correctly rounded divide
+ *   ray = camera.cast_ray(u, v)                      camera.rs:84-89
+ *   hit = world.hit(&ray)                            common.rs:237-258, t_min 0.001
+ * No RNG is involved.  width - 1 == 0 or height - 1 == 0 divides by zero as a
+ * frame does: the infinite or NaN ray hits nothing.  The hit is World::hit's
+ * winner, ties included: the lowest sphere index at equal t, the first
+ * triangle at equal t, and a triangle at the spheres' closest t beats the
+ * sphere.  RT_ACCEL_BRUTE and RT_ACCEL_BVH give identical bits.
+ *
+ * Records are stored top row first like every frame: index
+ * (height - 1 - row) * width + col.  A rectangle x0, y0, w, h in frame
+ * coordinates (y0 counted from the top row) restricts a call to those pixels;
+ * the output then holds w * h records (or pixels), the rectangle's top row
+ * first.  0, 0, 0, 0 is the whole frame.
+ *
+ * Calls take the handle's lock like frames, use the device's resident scene
+ * (uploaded on first use and again after rt_world_set_*_material) and are
+ * ordered against frames and passes on other streams as frames are.  They
+ * never read anything that was built for an earlier camera. */
+typedef struct RtFirstHit {
+  uint32_t prim;      /* 0: no hit.  1 + i: sphere i (file order, rt_world_sphere's i).
+                         1 + rt_world_num_spheres + j: triangle j (rt_world_triangle's j) */
+  float t;            /* hit.t; +inf for no hit */
+  float normal[3];    /* hit.normal as World::hit returns it (sphere: ((p - c) / r).normalize(),
+                         so a negative radius flips it; triangle: its stored normal); 0 0 0 for no hit */
+  float position[3];  /* hit.position = ray.at(t); 0 0 0 for no hit */
+} RtFirstHit;
+
+/* Views of a record as RGBA8.  Every step is one rounded f32 operation,
+ * unfused; `as u8` is Rust's saturating cast, as in the frame resolve.  Alpha
+ * is 255; a no-hit pixel is 0, 0, 0 in every view.
+ *   RT_VIEW_NORMAL: channel k = ((n_k * 0.5f) + 0.5f) * 255.999f as u8
+ *   RT_VIEW_DEPTH:  r = g = b = (1.0f / (1.0f + t)) * 255.999f as u8
+ *   RT_VIEW_ALBEDO: channel = c_k * 255.999f as u8, c the hit primitive's
+ *                   current material colour (Dielectric: 1, 1, 1, the colour
+ *                   its scatter returns, materials.rs:96)
+ *   RT_VIEW_PRIM:   h = prim * 2654435761u (mod 2^32); r, g, b = h >> 24,
+ *                   (h >> 16) & 255, (h >> 8) & 255 */
+enum { RT_VIEW_NORMAL = 0, RT_VIEW_DEPTH = 1, RT_VIEW_ALBEDO = 2, RT_VIEW_PRIM = 3 };
+
+typedef struct RtFirstHitOptions {
+  float su, sv;              /* [0, 1); default 0.5, 0.5 */
+  uint32_t x0, y0, w, h;     /* rectangle, y0 from the top; all 0 = whole frame */
+  int32_t device;            /* -1 = current */
+  int32_t accel;             /* RT_ACCEL_*: BRUTE and BVH give identical bits */
+} RtFirstHitOptions;
+
+/* su = sv = 0.5, the whole frame, device -1, RT_ACCEL_AUTO. */
+void rt_first_hit_default_options(RtFirstHitOptions *opts);
+/* Every call below: opts NULL = the defaults; returns 0 or a negative error
+ * with rt_last_error set.  Arguments are checked before a device is looked
+ * for: a null handle or output; a zero frame size or width * height >= 2^31; a
+ * rectangle that leaves the frame or has exactly one of w, h zero; su or sv
+ * outside [0, 1) (NaN included); an unknown view or accel; a pick outside the
+ * frame.  Without a GPU every call fails. */
+/* Records to host memory (synchronous) ... */
+int rt_first_hit(const Rust_WorldHandle *handle, size_t width, size_t height,
+                 const RtFirstHitOptions *opts, RtFirstHit *records);
+/* ... or to DEVICE memory on hip_stream (NULL = the library's stream): only
+ * enqueued, no host wait. */
+int rt_first_hit_device(const Rust_WorldHandle *handle, size_t width, size_t height,
+                        const RtFirstHitOptions *opts, void *d_records, void *hip_stream);
+/* One pixel, col from the left and row from the top: the record of that pixel
+ * (a 1 x 1 rectangle; the rectangle in opts is ignored).  Synchronous. */
+int rt_first_hit_pick(const Rust_WorldHandle *handle, size_t width, size_t height, size_t col,
+                      size_t row, const RtFirstHitOptions *opts, RtFirstHit *out);
+/* A view (RT_VIEW_*) of the same pixels as RGBA8, to host memory / to device
+ * memory; no record buffer is needed. */
+int rt_first_hit_view(const Rust_WorldHandle *handle, size_t width, size_t height,
+                      const RtFirstHitOptions *opts, int view, Rust_ColorU8 *pixels);
+int rt_first_hit_view_device(const Rust_WorldHandle *handle, size_t width, size_t height,
+                             const RtFirstHitOptions *opts, int view, void *d_rgba,
+                             void *hip_stream);
+
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).
  * That launch must have been rendered with RT_FLAG_KEEP_SAMPLES.  Output

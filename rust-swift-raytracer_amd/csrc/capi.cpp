@@ -508,6 +508,54 @@ long rt_adapt_read_active(RtAccum *acc, uint32_t *list, size_t cap) {
     return cam ? rtamd::adapt_read_active(*acc->state, *cam, list, cap) : -1;
 }
 
+// ---- first-hit records
+void rt_first_hit_default_options(RtFirstHitOptions *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->su = 0.5f;
+    o->sv = 0.5f;
+    o->device = -1;
+    o->accel = RT_ACCEL_AUTO;
+}
+
+// the handle's world and camera as they are now, or an error
+static int first_hit_call(const Rust_WorldHandle *h, size_t width, size_t height, const RtFirstHitOptions *opts,
+                          bool views, int view, void *d_out, void *hip_stream, void *host_out, const char *who,
+                          const rtamd::FirstHitPick *pick = nullptr) {
+    if (!h || !h->world || !h->camera) {
+        rtamd::set_error(std::string(who) + ": null world handle");
+        return -1;
+    }
+    return rtamd::first_hit(h->world->state, h->camera->cam, width, height, opts, views, view, d_out,
+                            static_cast<hipStream_t>(hip_stream), host_out, who, pick);
+}
+
+int rt_first_hit(const Rust_WorldHandle *h, size_t width, size_t height, const RtFirstHitOptions *opts,
+                 RtFirstHit *records) {
+    return first_hit_call(h, width, height, opts, false, 0, nullptr, nullptr, records, "rt_first_hit");
+}
+
+int rt_first_hit_device(const Rust_WorldHandle *h, size_t width, size_t height, const RtFirstHitOptions *opts,
+                        void *d_records, void *hip_stream) {
+    return first_hit_call(h, width, height, opts, false, 0, d_records, hip_stream, nullptr, "rt_first_hit_device");
+}
+
+int rt_first_hit_pick(const Rust_WorldHandle *h, size_t width, size_t height, size_t col, size_t row,
+                      const RtFirstHitOptions *opts, RtFirstHit *out) {
+    const rtamd::FirstHitPick pick{col, row};
+    return first_hit_call(h, width, height, opts, false, 0, nullptr, nullptr, out, "rt_first_hit_pick", &pick);
+}
+
+int rt_first_hit_view(const Rust_WorldHandle *h, size_t width, size_t height, const RtFirstHitOptions *opts,
+                      int view, Rust_ColorU8 *pixels) {
+    return first_hit_call(h, width, height, opts, true, view, nullptr, nullptr, pixels, "rt_first_hit_view");
+}
+
+int rt_first_hit_view_device(const Rust_WorldHandle *h, size_t width, size_t height, const RtFirstHitOptions *opts,
+                             int view, void *d_rgba, void *hip_stream) {
+    return first_hit_call(h, width, height, opts, true, view, d_rgba, hip_stream, nullptr,
+                          "rt_first_hit_view_device");
+}
+
 int rt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -29,6 +29,60 @@ size_t tile_row(size_t k, uint32_t row_block, uint32_t rank, uint32_t nranks) {
     return ((k / B) * nranks + rank) * B + k % B;
 }
 
+// What every kernel that casts a camera ray reads of a TraceParams, shared by
+// the frames (bind_scene below) and the first-hit calls (first_hit.cpp): the
+// scene's arrays, the camera's 12 floats, the frame size and its divisions.
+void bind_scene_arrays(const DeviceState *d, const CameraModel &cam, size_t width, size_t height, TraceParams &p) {
+    p.sph_hot = d->sph_hot.get(); p.sph_cold = d->sph_cold.get();
+    p.tri_hot = d->tri_hot.get(); p.tri_geo = d->tri_geo.get();
+    p.mats = d->mats.get();
+    const Vec3 cv[4] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical};
+    for (int i = 0; i < 4; ++i) { p.cam[3 * i] = cv[i].x; p.cam[3 * i + 1] = cv[i].y; p.cam[3 * i + 2] = cv[i].z; }
+    p.wden = (float)(uint64_t)(width - 1);   // (width-1) as f32 (common.rs:335)
+    p.hden = (float)(uint64_t)(height - 1);  // (height-1) as f32 (common.rs:336)
+    // the camera divisions through exactdiv.h: a denominator in [2^-40, 2^40]
+    // and its correctly rounded reciprocal (IEEE division on the host)
+    auto den_ok = [](float b) { return b >= 0x1p-40f && b <= 0x1p40f; };
+    p.xdiv_uv = den_ok(p.wden) && den_ok(p.hden);
+    p.wrcp = p.xdiv_uv ? 1.0f / p.wden : 0.0f;
+    p.hrcp = p.xdiv_uv ? 1.0f / p.hden : 0.0f;
+    p.nsph = d->nsph; p.nsph_padded = d->nsph_padded; p.ntri = d->ntri;
+    p.width = (uint32_t)width; p.height = (uint32_t)height;
+    p.sph_shade = d->sph_shade.get();
+    p.sph_kind = d->sph_kind.get();
+    p.div_width = make_fastdiv((uint32_t)width);
+}
+
+// The sphere tree in global memory with its bounds (p.nnodes != 0 from here on)
+void bind_sphere_tree(const WorldState &w, const DeviceState *d, TraceParams &p) {
+    const SphereBVH &bv = w.bvh;
+    p.bvh_nodes = d->bvh_nodes.get(); p.bvh_miss = d->bvh_miss.get();
+    p.bvh_prims = d->bvh_prims.get(); p.bvh_prim_id = d->bvh_prim_id.get();
+    p.big_hot = d->big_hot.get(); p.big_id = d->big_id.get();
+    p.nnodes = d->nnodes; p.nbig = d->nbig; p.nprims = d->nprims;
+    p.bvh_miss16 = d->bvh_miss16.get();
+    for (int k = 0; k < 3; ++k) p.bvh_c[k] = bv.centre[k];
+    p.bvh_r = bv.radius; p.bvh_rmax = bv.rmax; p.bvh_mag = bv.mag;
+    p.bvh_inv_rmin = env_u64("RT_AMD_LINEAR_E", 0) ? INFINITY : bv.inv_rmin;
+}
+
+// The static triangle tree (binary nodes), its records and grids (p.tnodes != 0)
+void bind_triangle_tree(const WorldState &w, const DeviceState *d, TraceParams &p) {
+    const TriangleBVH &tb = w.tbvh;
+    p.tbvh_nodes = d->tbvh_nodes.get();
+    p.tbvh_tris = d->tbvh_tris.get(); p.tbvh_loose = d->tbvh_loose.get();
+    p.tnodes = d->tnodes; p.ttris = d->ttris; p.tloose = d->tloose;
+    for (int k = 0; k < 3; ++k) {
+        p.tbvh_c[k] = tb.centre[k];
+        p.tbvh_oc[k] = tb.oc[k];
+        p.tq_base[k] = tb.qbox.base[k];
+        p.tq_step[k] = tb.qbox.step[k];
+    }
+    p.tq_nbase = tb.nbase;
+    p.tq_nstep = tb.nstep;
+    p.tbvh_r = tb.radius; p.tbvh_mag = std::max(tb.mag, w.tcells.mag);
+}
+
 namespace {
 
 // The per-camera arrays (camera records, host-built lists) are uploaded again
@@ -163,9 +217,7 @@ int plan_sample_storage(DeviceState *d, const RtRenderOptions &o, size_t width, 
 // Scene pointers, camera, dimensions and the division constants
 void bind_scene(DeviceState *d, const CameraModel &cam, size_t width, size_t height, const RtRenderOptions &o,
                 const SerialPass *sp, const uint32_t *d_replay, const FrameValues &f, TraceParams &p) {
-    p.sph_hot = d->sph_hot.get(); p.sph_cold = d->sph_cold.get();
-    p.tri_hot = d->tri_hot.get(); p.tri_geo = d->tri_geo.get();
-    p.mats = d->mats.get();
+    bind_scene_arrays(d, cam, width, height, p);
     p.samples = d->samples.get();
     p.job_counter = d->counter.get();
     p.job_counter_next = nullptr;
@@ -173,26 +225,11 @@ void bind_scene(DeviceState *d, const CameraModel &cam, size_t width, size_t hei
     // start over from a fill after them)
     if (sp) d->cset_clean[0] = d->cset_clean[1] = false;
     p.replay = d_replay ? d_replay : d->replay.get();
-    const Vec3 cv[4] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical};
-    for (int i = 0; i < 4; ++i) { p.cam[3 * i] = cv[i].x; p.cam[3 * i + 1] = cv[i].y; p.cam[3 * i + 2] = cv[i].z; }
-    p.wden = (float)(uint64_t)(width - 1);   // (width-1) as f32 (common.rs:335)
-    p.hden = (float)(uint64_t)(height - 1);  // (height-1) as f32 (common.rs:336)
-    // the camera divisions through exactdiv.h: a denominator in [2^-40, 2^40]
-    // and its correctly rounded reciprocal (IEEE division on the host)
-    auto den_ok = [](float b) { return b >= 0x1p-40f && b <= 0x1p40f; };
-    p.xdiv_uv = den_ok(p.wden) && den_ok(p.hden);
-    p.wrcp = p.xdiv_uv ? 1.0f / p.wden : 0.0f;
-    p.hrcp = p.xdiv_uv ? 1.0f / p.hden : 0.0f;
-    p.nsph = d->nsph; p.nsph_padded = d->nsph_padded; p.ntri = d->ntri;
-    p.width = (uint32_t)width; p.height = (uint32_t)height; p.spp = f.spp;
+    p.spp = f.spp;
     p.depth = o.max_ray_bounces;
     p.mode = f.replay ? (uint32_t)RT_RNG_REPLAY : (uint32_t)RT_RNG_COUNTER;
     p.seed = o.seed;
     p.ablate = (uint32_t)env_u64("RT_AMD_ABLATE", 0);
-    p.sph_shade = d->sph_shade.get();
-    p.sph_kind = d->sph_kind.get();
-
-    p.div_width = make_fastdiv((uint32_t)width);
     p.div_spp = make_fastdiv(f.spp ? f.spp : 1);
     p.div_rowblock = make_fastdiv(f.B);
     // node visits per lane per loop iteration of a sliced walk (A/B on C5, 8
@@ -209,12 +246,7 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
                        TraceParams &p) {
     f.use_bvh = d->nnodes > 0 && o.accel != RT_ACCEL_BRUTE;
     if (f.use_bvh) {
-        const SphereBVH &bv = w.bvh;
-        p.bvh_nodes = d->bvh_nodes.get(); p.bvh_miss = d->bvh_miss.get();
-        p.bvh_prims = d->bvh_prims.get(); p.bvh_prim_id = d->bvh_prim_id.get();
-        p.big_hot = d->big_hot.get(); p.big_id = d->big_id.get();
-        p.nnodes = d->nnodes; p.nbig = d->nbig; p.nprims = d->nprims;
-        p.bvh_miss16 = d->bvh_miss16.get();
+        bind_sphere_tree(w, d, p);
         // The LDS layout: corner records for the sphere-only frame kernels when
         // they fit (RT_AMD_CORNER=0: box records, for A/B runs and tests), box
         // records for the SERIAL passes and everything else; RT_AMD_LDS=0 or
@@ -226,9 +258,6 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
         // enters them, for A/B runs and tests)
         f.leaf_defer = f.corner_img != nullptr && env_u64("RT_AMD_LEAF_DEFER", 1) != 0;
         p.use_lds = lds_on && (d->lds_bytes > 0 || f.corner_img != nullptr);
-        for (int k = 0; k < 3; ++k) p.bvh_c[k] = bv.centre[k];
-        p.bvh_r = bv.radius; p.bvh_rmax = bv.rmax; p.bvh_mag = bv.mag;
-        p.bvh_inv_rmin = env_u64("RT_AMD_LINEAR_E", 0) ? INFINITY : bv.inv_rmin;
         // sphere-only scenes: primary rays test their pixel's candidates
         if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 && gpu_lists()) {
             bool ok = false;
@@ -335,18 +364,7 @@ int bind_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, 
             }
             for (int k = 0; k < 3; ++k) { p.cq_base[k] = w.ctree.qbox.base[k]; p.cq_step[k] = w.ctree.qbox.step[k]; }
         }
-        const TriangleBVH &tb = w.tbvh;
-        p.tbvh_nodes = d->tbvh_nodes.get();
-        p.tbvh_tris = d->tbvh_tris.get(); p.tbvh_loose = d->tbvh_loose.get();
-        p.tnodes = d->tnodes; p.ttris = d->ttris; p.tloose = d->tloose;
-        for (int k = 0; k < 3; ++k) {
-            p.tbvh_c[k] = tb.centre[k];
-            p.tbvh_oc[k] = tb.oc[k];
-            p.tq_base[k] = tb.qbox.base[k];
-            p.tq_step[k] = tb.qbox.step[k];
-        }
-        p.tq_nbase = tb.nbase;
-        p.tq_nstep = tb.nstep;
+        bind_triangle_tree(w, d, p);
         if (d->tw_nodes) {
             p.tw_nodes = d->tw_nodes.get();
             p.tw_depth = d->tw_depth;
@@ -364,7 +382,6 @@ int bind_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, 
             // on C5: 16 -> 166.1 ms, 20 -> 163.9, 24 -> 163.5, 28 -> 164.4, 32 -> 166.4)
             p.wsteps = (uint32_t)std::max<uint64_t>(1, env_u64("RT_AMD_WSTEPS", 24));
         }
-        p.tbvh_r = tb.radius; p.tbvh_mag = std::max(tb.mag, w.tcells.mag);
     }
     return 0;
 }
@@ -706,6 +723,17 @@ int queue_frame_stats(DeviceState *d, hipStream_t s, const FrameValues &f, const
 }
 
 }  // namespace
+
+// bind_triangle_search for a caller outside this unit (first_hit.cpp): the
+// static tree and, where they apply, the camera-origin records and primary
+// strip lists, made current for (cam, width, height) as for a frame.
+int bind_primary_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
+                                 int32_t accel, hipStream_t stream, hipStream_t s, TraceParams &p) {
+    RtRenderOptions o{};
+    o.accel = accel;
+    FrameValues f;
+    return bind_triangle_search(w, d, cam, width, height, o, stream, s, f, p);
+}
 
 int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t height,
                  const RtRenderOptions &o, uint32_t *d_out, hipStream_t stream,

@@ -296,6 +296,22 @@ struct AdaptTail {
 };
 hipError_t launch_trace_adapt(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
                               const AdaptTail &tail);
+// First-hit records (first_hit.hip): one lane per pixel of the
+// rectangle (x0, y0 from the top row, w x h, inside the p.width x p.height
+// frame) casts the frame's primary ray with its two draws replaced by su, sv
+// and stops after World::hit.  p: the scene, the camera, wden / hden and the
+// frame size; p.nnodes / p.tnodes != 0 select the sphere tree (from global
+// memory) and the static triangle tree, else brute force.  view kViewNone:
+// out gets w x h 32-byte records (RtFirstHit), the rectangle's top row first;
+// else w x h RGBA8 words of that view.  A plain grid: no job queue, no LDS.
+enum : uint32_t { kViewNormal = 0, kViewDepth = 1, kViewAlbedo = 2, kViewPrim = 3, kViewNone = 0xFFFFFFFFu };
+struct FirstHitTail {
+    void *out;
+    float su, sv;
+    uint32_t x0, y0, w, h;
+    uint32_t view;
+};
+hipError_t launch_first_hit(const TraceParams &p, const FirstHitTail &tail, hipStream_t stream);
 // The adaptive accumulator's list kernels (adapt.hip).  iota: list[i] = i.
 // select: one thread per entry i < n of list: count[list[i]] = N and, with
 // decide, keep[i] = 0 iff the pixel converged by the rule of DESIGN.md 5.7

@@ -19,6 +19,7 @@
 
 struct RtRenderOptions;
 struct RtRenderStats;
+struct RtFirstHitOptions;
 
 namespace rtamd {
 
@@ -126,6 +127,7 @@ struct DeviceState {
     DevBuf<uint32_t> out;                                       // RGBA8 tile (host path)
     DevBuf<uint32_t> tile;                                      // multi-device: this rank's tile
     DevBuf<uint32_t> gath;                                      // multi-device root: gathered tiles
+    DevBuf<uint32_t> first_hit;                                 // first-hit records / views (host path)
     hipEvent_t done = nullptr;       // end of the last frame enqueued on this device ...
     hipStream_t done_stream = nullptr;  // ... and the stream it was enqueued on
     DevBuf<uint32_t> replay;
@@ -340,6 +342,17 @@ long adapt_active(AccumState &a, const CameraModel &cam);
 int adapt_read_counts(AccumState &a, const CameraModel &cam, uint32_t *counts);
 int adapt_read_sumsq(AccumState &a, const CameraModel &cam, float *sumsq);
 long adapt_read_active(AccumState &a, const CameraModel &cam, uint32_t *list, size_t cap);
+// First-hit records (rt_first_hit_*, include/raytracer_amd.h) of
+// the rectangle in opts (nullptr: the defaults) for the camera given, on the
+// device's resident scene.  views: RT_VIEW_* `view` as RGBA8, else 32-byte
+// records.  d_out (device memory, on stream; only enqueued) or host_out (waits).
+// pick: the rectangle is that one pixel (row from the top).  who: the entry
+// point, for the messages.  Checks every argument with a message before it
+// looks for a device.
+struct FirstHitPick { size_t col, row; };
+int first_hit(WorldState &w, const CameraModel &cam, size_t width, size_t height, const RtFirstHitOptions *opts,
+              bool views, int view, void *d_out, hipStream_t stream, void *host_out, const char *who,
+              const FirstHitPick *pick = nullptr);
 // Waits for device d's pending counted frame and fills stats from it.
 int collect_frame_stats(DeviceState *d, RtRenderStats *stats);
 

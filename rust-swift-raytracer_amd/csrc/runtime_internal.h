@@ -53,6 +53,19 @@ static constexpr uint32_t kPixtabParts = 64;  // the pixel table pass's (zeroed 
 // and occupancy decisions.  Selects the device.
 int device_for(WorldState &w, int want, DeviceState *&out);
 
+// frame.cpp: the parts of a TraceParams that do not depend on the kind of
+// launch -- the scene's arrays with the camera and the frame size, the sphere
+// tree (global-memory walk) and the static triangle tree
+void bind_scene_arrays(const DeviceState *d, const CameraModel &cam, size_t width, size_t height, TraceParams &p);
+void bind_sphere_tree(const WorldState &w, const DeviceState *d, TraceParams &p);
+void bind_triangle_tree(const WorldState &w, const DeviceState *d, TraceParams &p);
+// ... and a frame's whole triangle search for (cam, width, height): that tree
+// plus the camera-origin records and primary strip lists, rebuilt when the
+// camera, the frame size or the records changed (stream: the caller's, may be
+// null; s: the stream the launch goes to)
+int bind_primary_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
+                                 int32_t accel, hipStream_t stream, hipStream_t s, TraceParams &p);
+
 // primary_lists.cpp
 bool gpu_lists();      // RT_AMD_GPU_LISTS
 bool gpu_tri_lists();  // RT_AMD_GPU_TRI_LISTS

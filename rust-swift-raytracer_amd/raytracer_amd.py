@@ -23,6 +23,7 @@ ACCEL_AUTO, ACCEL_BRUTE, ACCEL_BVH = 0, 1, 2
 FLAG_KEEP_SAMPLES = 1
 FLAG_SERIAL_CHECK = 2
 DEFAULT_SEED = 2547549
+VIEW_NORMAL, VIEW_DEPTH, VIEW_ALBEDO, VIEW_PRIM = 0, 1, 2, 3
 
 # Every symbol declared in include/raytracer.h and include/raytracer_amd.h.
 EXPORTS = (
@@ -38,6 +39,8 @@ EXPORTS = (
     "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active", "rt_leaf_defer",
     "rt_camera_new_with_vertical_fov", "rt_camera_new_look_at", "rt_camera_from_floats",
     "rt_camera_translate", "rt_camera_free", "rt_primary_tri_lists", "rt_camera_record_builds",
+    "rt_first_hit_default_options", "rt_first_hit", "rt_first_hit_device", "rt_first_hit_pick",
+    "rt_first_hit_view", "rt_first_hit_view_device",
 )
 
 
@@ -73,6 +76,22 @@ class AccumOptions(C.Structure):
 
 class AdaptOptions(C.Structure):
     _fields_ = [("tolerance", C.c_float), ("bias", C.c_float), ("min_samples", C.c_uint32)]
+
+
+class RtFirstHit(C.Structure):
+    """One pixel's first hit (raytracer_amd.h RtFirstHit): prim 0 = no hit, 1 + i =
+    sphere i, 1 + num_spheres + j = triangle j."""
+    _fields_ = [("prim", C.c_uint32), ("t", C.c_float), ("normal", C.c_float * 3),
+                ("position", C.c_float * 3)]
+
+
+# the same 32 bytes as a numpy structured dtype (World.first_hit's arrays)
+FIRST_HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("normal", "<f4", (3,)), ("position", "<f4", (3,))])
+
+
+class FirstHitOptions(C.Structure):
+    _fields_ = [("su", C.c_float), ("sv", C.c_float), ("x0", C.c_uint32), ("y0", C.c_uint32),
+                ("w", C.c_uint32), ("h", C.c_uint32), ("device", C.c_int32), ("accel", C.c_int32)]
 
 
 class RenderStats(C.Structure):
@@ -218,6 +237,21 @@ def lib(path=None):
             L.rt_adapt_read_sumsq.argtypes = [C.c_void_p, fp]
             L.rt_adapt_read_active.restype = C.c_long
             L.rt_adapt_read_active.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t]
+        if hasattr(L, "rt_first_hit"):  # (likewise)
+            FO = C.POINTER(FirstHitOptions)
+            L.rt_first_hit_default_options.restype = None
+            L.rt_first_hit_default_options.argtypes = [FO]
+            L.rt_first_hit.restype = C.c_int
+            L.rt_first_hit.argtypes = [H, C.c_size_t, C.c_size_t, FO, C.c_void_p]
+            L.rt_first_hit_device.restype = C.c_int
+            L.rt_first_hit_device.argtypes = [H, C.c_size_t, C.c_size_t, FO, C.c_void_p, C.c_void_p]
+            L.rt_first_hit_pick.restype = C.c_int
+            L.rt_first_hit_pick.argtypes = [H, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, FO,
+                                            C.POINTER(RtFirstHit)]
+            L.rt_first_hit_view.restype = C.c_int
+            L.rt_first_hit_view.argtypes = [H, C.c_size_t, C.c_size_t, FO, C.c_int, C.POINTER(ColorU8)]
+            L.rt_first_hit_view_device.restype = C.c_int
+            L.rt_first_hit_view_device.argtypes = [H, C.c_size_t, C.c_size_t, FO, C.c_int, C.c_void_p, C.c_void_p]
         _libs[path] = L
     return _libs[path]
 
@@ -463,6 +497,68 @@ class World:
         if rc != 0:
             raise RenderError(f"rt_render_device failed ({rc}): {self._L.rt_last_error().decode()}")
         return st.as_dict() if stats else None
+
+
+    # ---- first-hit records (rt_first_hit_*)
+    def _first_hit_options(self, su, sv, rect, accel, device):
+        o = FirstHitOptions()
+        self._L.rt_first_hit_default_options(C.byref(o))
+        o.su, o.sv, o.accel, o.device = su, sv, accel, device
+        if rect is not None:
+            o.x0, o.y0, o.w, o.h = rect
+        return o
+
+    @staticmethod
+    def _first_hit_shape(width, height, rect):
+        return (height, width) if rect is None or tuple(rect) == (0, 0, 0, 0) else (rect[3], rect[2])
+
+    def _first_hit_check(self, rc, what):
+        if rc != 0:
+            raise RenderError(f"{what} failed ({rc}): {self._L.rt_last_error().decode()}")
+
+    def first_hit(self, width, height, su=0.5, sv=0.5, rect=None, accel=ACCEL_AUTO, device=-1):
+        """rt_first_hit: what each pixel's primary ray (sub-pixel offsets su, sv, no
+        RNG) hits first -> FIRST_HIT_DTYPE[h, w], top row first.  rect = (x0, y0, w,
+        h), y0 from the top row: only those pixels."""
+        o = self._first_hit_options(su, sv, rect, accel, device)
+        out = np.zeros(self._first_hit_shape(width, height, rect), FIRST_HIT_DTYPE)
+        self._first_hit_check(self._L.rt_first_hit(self._h, width, height, C.byref(o), out.ctypes.data), "rt_first_hit")
+        return out
+
+    def first_hit_device(self, width, height, out_ptr: int, stream_ptr: int = 0, su=0.5, sv=0.5, rect=None,
+                         accel=ACCEL_AUTO, device=-1):
+        """rt_first_hit_device: the records into device memory (32 bytes per pixel),
+        only enqueued on the stream."""
+        o = self._first_hit_options(su, sv, rect, accel, device)
+        self._first_hit_check(self._L.rt_first_hit_device(self._h, width, height, C.byref(o), C.c_void_p(out_ptr),
+                                                          C.c_void_p(stream_ptr or None)), "rt_first_hit_device")
+
+    def pick(self, width, height, col, row, su=0.5, sv=0.5, accel=ACCEL_AUTO, device=-1):
+        """rt_first_hit_pick: the record of the pixel at col (from the left), row (from
+        the top) -> a FIRST_HIT_DTYPE scalar (rec["prim"]: 0 none, 1 + i sphere i,
+        1 + num_spheres + j triangle j)."""
+        o = self._first_hit_options(su, sv, None, accel, device)
+        rec = RtFirstHit()
+        self._first_hit_check(self._L.rt_first_hit_pick(self._h, width, height, col, row, C.byref(o), C.byref(rec)),
+                              "rt_first_hit_pick")
+        return np.frombuffer(bytes(rec), FIRST_HIT_DTYPE)[0]
+
+    def first_hit_view(self, width, height, view, su=0.5, sv=0.5, rect=None, accel=ACCEL_AUTO, device=-1):
+        """rt_first_hit_view: VIEW_NORMAL / VIEW_DEPTH / VIEW_ALBEDO / VIEW_PRIM of the
+        same pixels -> uint8[h, w, 4]."""
+        o = self._first_hit_options(su, sv, rect, accel, device)
+        px = np.zeros(self._first_hit_shape(width, height, rect) + (4,), np.uint8)
+        self._first_hit_check(self._L.rt_first_hit_view(self._h, width, height, C.byref(o), view,
+                                                        px.ctypes.data_as(C.POINTER(ColorU8))), "rt_first_hit_view")
+        return px
+
+    def first_hit_view_device(self, width, height, view, out_ptr: int, stream_ptr: int = 0, su=0.5, sv=0.5,
+                              rect=None, accel=ACCEL_AUTO, device=-1):
+        """rt_first_hit_view_device: the view into device memory (RGBA8), only enqueued."""
+        o = self._first_hit_options(su, sv, rect, accel, device)
+        self._first_hit_check(self._L.rt_first_hit_view_device(self._h, width, height, C.byref(o), view,
+                                                               C.c_void_p(out_ptr), C.c_void_p(stream_ptr or None)),
+                              "rt_first_hit_view_device")
 
 
 class Accumulator:
