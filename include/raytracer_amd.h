@@ -419,6 +419,14 @@ long rt_read_samples(const Rust_WorldHandle *handle, int device, float *out, siz
  * bit-identical frames.  Negative: an error. */
 int rt_leaf_defer(const Rust_WorldHandle *handle, int device);
 
+/* Diagnostics: 1 when the LAST frame trace launch on `device` (-1 = current)
+ * ran the plain instance of the lean deferred-leaf kernel, in which the
+ * launch's constants are compiled in (COUNTER frames of one
+ * rank with primary sphere lists whose chunks resolve with plane lanes,
+ * RT_AMD_PLAIN=0 turns it off), 0 when it ran another instance.  Both give
+ * bit-identical frames.  Negative: an error. */
+int rt_trace_plain(const Rust_WorldHandle *handle, int device);
+
 /* Frees a handle from load_world (the reference never frees, lib.rs:42-45). */
 void rt_free_world(Rust_WorldHandle *handle);
 

@@ -200,6 +200,14 @@ int rt_render_device(const Rust_WorldHandle *h, size_t width, size_t height,
                                static_cast<hipStream_t>(hip_stream), stats);
 }
 
+int rt_trace_plain(const Rust_WorldHandle *h, int device) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_trace_plain: null argument");
+        return -1;
+    }
+    return rtamd::trace_plain(h->world->state, device);
+}
+
 int rt_leaf_defer(const Rust_WorldHandle *h, int device) {
     if (!h || !h->world) {
         rtamd::set_error("rt_leaf_defer: null argument");

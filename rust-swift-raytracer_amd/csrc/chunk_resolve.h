@@ -13,9 +13,10 @@ namespace {
 __device__ __forceinline__ uint32_t resolve_channel(const TraceParams &p, float sum) {
     return sat_u8(__builtin_sqrtf(sum * p.inv_spp) * 255.999f);
 }
+template <bool kPlain = false>
 __device__ __forceinline__ void resolve_store_u8(const TraceParams &p, uint32_t lp, uint32_t R, uint32_t G,
                                                  uint32_t B) {
-    const uint32_t q = fdiv(lp, p.div_width);
+    const uint32_t q = fdiv<kPlain>(lp, p.div_width);
     const uint32_t col = lp - q * p.width;
     p.out[(size_t)(p.slab_row0 + q) * p.width + col] = R | (G << 8) | (B << 16) | (p.alpha_u8 << 24);
 }
@@ -55,15 +56,19 @@ __device__ __forceinline__ size_t resolve_index(const TraceParams &p, uint32_t l
     const uint32_t col = lp - q * p.width;
     return (size_t)(p.slab_row0 + q) * p.width + col;
 }
-template <bool kPlaneLanes, bool kAccum = false>
+// kPlain (the plain instance, render.h trace_plain_ok): every chunk of the
+// launch has the plane-lane shape and both dividers are in their general form,
+// so neither is tested and the pixel-lane loop is not compiled.
+template <bool kPlaneLanes, bool kAccum = false, bool kPlain = false>
 __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float *ring, uint32_t plane,
                                               uint32_t off, uint32_t base, uint32_t len,
                                               uint32_t lane, float *sums = nullptr) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const uint32_t spp = p.spp;
-    const uint32_t np = fdiv(len, p.div_spp), pix0 = fdiv(base, p.div_spp);
-    if (kPlaneLanes && 3u * np <= kWave && (spp & 3u) == 0) {
+    static_assert(!kPlain || (kPlaneLanes && !kAccum), "the plain instance: plane lanes, frames");
+    const uint32_t np = fdiv<kPlain>(len, p.div_spp), pix0 = fdiv<kPlain>(base, p.div_spp);
+    if (kPlaneLanes && (kPlain || (3u * np <= kWave && (spp & 3u) == 0))) {
         const uint32_t c = lane >= np ? (lane >= 2u * np ? 2u : 1u) : 0u;
         const uint32_t g = lane - c * np;
         const bool on = lane < 3u * np;
@@ -98,7 +103,7 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
         const uint32_t ch = resolve_channel(p, acc);
         const uint32_t G = (uint32_t)__shfl((int)ch, (int)(lane < np ? np + lane : lane));
         const uint32_t B = (uint32_t)__shfl((int)ch, (int)(lane < np ? 2u * np + lane : lane));
-        if (lane < np) resolve_store_u8(p, pix0 + lane, ch, G, B);
+        if (lane < np) resolve_store_u8<kPlain>(p, pix0 + lane, ch, G, B);
         return;
     }
     for (uint32_t i = lane; i < np; i += kWave) {

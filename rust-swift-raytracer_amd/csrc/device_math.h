@@ -132,6 +132,14 @@ __device__ __forceinline__ uint4 uniform_load_u4(const uint4 *base, uint32_t i) 
 }
 
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) { return fastdiv_apply(n, f); }
+// kGeneral: the divisor is known to be above 1 (f.one == 0, render.h
+// trace_plain_ok), so the flag is neither loaded nor tested
+template <bool kGeneral>
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) {
+    if (!kGeneral) return fastdiv_apply(n, f);
+    const uint32_t t = __umulhi(n, f.m);
+    return (t + ((n - t) >> 1)) >> f.s;
+}
 
 constexpr uint32_t kNodeEndDev = 0xFFFFFFFFu;  // bvh.h kNodeEnd
 constexpr uint32_t kLeafBitDev = 0x80000000u;  // bvh.h kLeafBit

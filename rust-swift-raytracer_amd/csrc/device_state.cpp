@@ -184,6 +184,17 @@ static int choose_lds_layout(const WorldState &w, DeviceState *d, size_t lds_cap
                 }
             }
             if (fits) {
+                // (the plain twin runs only at the deferred instance's occupancy: the
+                // launch plans are made with that one)
+                TraceVariant v = trace_variant(kSearchLdsCorner, false, tri, kKindLean, true);
+                int blocks = 0;
+                v.plain = true;
+                if (trace_plain(v) && trace_occupancy(&blocks, v, corner) == hipSuccess)
+                    d->plain_fits = blocks == d->defer_blocks_per_cu;
+                else
+                    (void)hipGetLastError();
+            }
+            if (fits) {
                 HIP_TRY(d->bvh_corner.upload(bv.corner));
                 d->corner_bytes = corner;
             }

@@ -128,6 +128,7 @@ struct FrameValues {
     bool use_bvh = false;              // bind_sphere_search
     const uint4 *corner_img = nullptr; // the LDS tree as corner records (sphere-only frames), else box records
     bool leaf_defer = false;           // ... walked with deferred leaf tests (render.h trace_variant)
+    bool plain = false;                // ... by the plain instance where a launch allows it (render.h trace_plain_ok)
     bool primary_lists = false;        // the frame's primary rays use candidate lists (spheres or triangles)
     bool use_tbvh = false;             // bind_triangle_search
     int ptl_where = 0;                 // rt_primary_tri_lists: 0 none, 1 host build, 2 device build
@@ -257,6 +258,8 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
         // (RT_AMD_LEAF_DEFER=0: the lean corner kernel tests leaves where it
         // enters them, for A/B runs and tests)
         f.leaf_defer = f.corner_img != nullptr && env_u64("RT_AMD_LEAF_DEFER", 1) != 0;
+        // (RT_AMD_PLAIN=0: every launch runs the generic instance, for A/B runs and tests)
+        f.plain = f.leaf_defer && d->plain_fits && env_u64("RT_AMD_PLAIN", 1) != 0;
         p.use_lds = lds_on && (d->lds_bytes > 0 || f.corner_img != nullptr);
         // sphere-only scenes: primary rays test their pixel's candidates
         if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 && gpu_lists()) {
@@ -649,8 +652,10 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
                 HIP_TRY(launch_trace_adapt(p, (uint32_t)blocks, s, f.corner_img,
                                            AdaptTail{tail.sums, ap->acc->sumsq.get(), ap->list + r0, tail.n0, tail.stride}));
             else if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, f.corner_img, tail));
-            else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, f.corner_img, f.leaf_defer));
+            else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, f.corner_img, f.leaf_defer, f.plain));
             d->last_leaf_defer = trace_leaf_defer(f.tv);
+            // (the launch's own parameters decide: chunk, ring and gj32 are set per launch)
+            d->last_plain = !ap && trace_plain(trace_variant(p, f.corner_img != nullptr, f.leaf_defer, f.plain));
             d->last_ptl = f.ptl_where;
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
@@ -872,6 +877,14 @@ int leaf_defer(WorldState &w, int device) {
     int rc = device_for(w, device, d);
     if (rc) return rc;
     return d->last_leaf_defer;
+}
+
+int trace_plain(WorldState &w, int device) {
+    std::lock_guard<std::recursive_mutex> lock(w.mu);  // (device_for may add a device)
+    DeviceState *d = nullptr;
+    int rc = device_for(w, device, d);
+    if (rc) return rc;
+    return d->last_plain ? 1 : 0;
 }
 
 int primary_tri_lists(WorldState &w, int device) {

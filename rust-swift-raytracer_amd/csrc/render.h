@@ -222,12 +222,15 @@ enum : int { kSearchBrute = 0, kSearchGlobal = 1, kSearchLdsBox = 2, kSearchLdsC
 enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2, kKindAccum = 3, kKindAdapt = 4 };
 //   defer:  the corner walk defers its leaf tests to shared leaf passes
 //           (DESIGN.md 5.2 "deferred leaves")
+//   plain:  the deferred-leaf kernel with the launch's constants compiled in
+//           (trace_plain_ok; DESIGN.md 5.1 "the plain instance")
 struct TraceVariant {
     int search;
     bool step;
     int mesh;
     int kind;
     bool defer = false;
+    bool plain = false;
     bool lds() const { return search >= kSearchLdsBox; }
 };
 // The instance that serves a scene of family `mesh` (0-3) searched as `search`:
@@ -257,12 +260,33 @@ inline TraceVariant trace_variant(const TraceParams &p, bool corner, bool defer)
                          defer);
 }
 
+// What the plain instance (trace_body's kPlain) takes for granted about its
+// launch; p as launch_trace gets it, every field set.  The one place this
+// rule lives: a launch that fails any line runs the instance it ran before.
+// Every chunk then has the plane-lane resolve's shape (chunk_resolve.h): a
+// partition's last chunk is shorter than p.chunk, never longer.
+inline bool trace_plain_ok(const TraceParams &p) {
+    return p.mode == kRngCounter && p.stats == nullptr && p.ring != nullptr && p.gj32 != 0 && p.xdiv_uv != 0 &&
+           p.spl != nullptr && p.walk_min != 0 && p.ablate == 0 && p.nnodes > 1 && p.div_spp.one == 0 &&
+           p.div_width.one == 0 && (p.spp & 3u) == 0 && p.chunk % p.spp == 0 && 3u * (p.chunk / p.spp) <= 64u;
+}
+// ... with plain: the plain instance is wanted (RT_AMD_PLAIN, on by default).
+// It exists for the deferred-leaf kernel alone, and only a launch that
+// satisfies trace_plain_ok runs it.
+inline TraceVariant trace_variant(const TraceParams &p, bool corner, bool defer, bool plain) {
+    TraceVariant v = trace_variant(p, corner, defer);
+    v.plain = plain && v.defer && trace_plain_ok(p);
+    return v;
+}
+
 // corner (sphere-only frames with p.use_lds): the corner records (bvh.h
 // SphereBVH::corner, 8 uint4 per node) the workgroups stage instead of the box
 // records (the corner-record kernel instances; trace_corner_lds bytes each).
-// Runs instance trace_variant(p, corner != nullptr, defer).
+// Runs instance trace_variant(p, corner != nullptr, defer, plain).
 hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream,
-                        const uint4 *corner = nullptr, bool defer = false);
+                        const uint4 *corner = nullptr, bool defer = false, bool plain = false);
+// v is the plain instance and the build has it
+bool trace_plain(TraceVariant v);
 // Pending leaves per lane of instance v's deferred walk; 0: it tests leaves
 // where it enters them.
 int trace_leaf_defer(TraceVariant v);

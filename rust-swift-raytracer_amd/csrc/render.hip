@@ -89,6 +89,20 @@ void trace_kernel(CornerParams c) {
     trace_body<true, true, false, 0, kCount, false, true, false, false, kLeafDeferC>(c.p, c.image);
 }
 }  // namespace deferred
+// The deferred-leaf kernel with the launch's constants compiled in
+// (trace_body's kPlain; launches that satisfy render.h trace_plain_ok): an
+// instance of its own beside the one above, which stays the code it was and
+// runs every other launch (RT_AMD_PLAIN=0: all of them).  Same name and
+// parameter list again.
+namespace plain {
+template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial = false>
+__global__ __launch_bounds__(trace_threads(true, 0, 0))
+__attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(true, 0, 0), 8)))
+void trace_kernel(CornerParams c) {
+    static_assert(kBvh && kLds && !kStep && kMesh == 0 && !kCount && !kSerial, "plain: the lean deferred-leaf kernel");
+    trace_body<true, true, false, 0, false, false, true, false, false, kLeafDeferC, true>(c.p, c.image);
+}
+}  // namespace plain
 }  // namespace corner
 
 // Accumulation passes (kKindAccum): the lean frame kernels' twins with
@@ -198,9 +212,9 @@ struct TraceInstance {
                        // whatever the search)
 };
 constexpr int kTraceKinds = 5;
-constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds * 2;  // search x step x mesh x kind x defer
+constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds * 2 * 2;  // search x step x mesh x kind x defer x plain
 constexpr int trace_index(TraceVariant v) {
-    return (((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind) * 2 + v.defer;
+    return ((((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind) * 2 + v.defer) * 2 + v.plain;
 }
 
 // an accumulation pass's kernel (kAdapt: an adaptive pass's)
@@ -212,15 +226,21 @@ static const void *pass_kernel() {
 
 template <int kJ>
 static TraceInstance trace_instance_at() {
-    constexpr int kI = kJ / 2;
-    constexpr bool kDeferred = kJ % 2 != 0;
+    constexpr int kI = kJ / 4;
+    constexpr bool kDeferred = kJ / 2 % 2 != 0, kPlain = kJ % 2 != 0;
     constexpr int kSearch = kI / (8 * kTraceKinds), kMesh = kI / kTraceKinds % 4, kKind = kI % kTraceKinds;
     constexpr bool kStep = kI / (4 * kTraceKinds) % 2 != 0, kCount = kKind == kKindCounting,
                    kSerial = kKind == kKindSerial, kAccum = kKind == kKindAccum, kAdapt = kKind == kKindAdapt;
     // (an accumulation pass runs at its lean twin's workgroup size)
     constexpr uint32_t threads =
         trace_threads(kSearch >= kSearchLdsBox, kMesh, kAccum || kAdapt ? (int)kKindLean : kKind);
-    if constexpr (kDeferred) {  // deferred leaves: the lean whole-walk corner kernel (render.h trace_variant)
+    if constexpr (kPlain) {  // the deferred-leaf kernel's plain twin (render.h trace_plain_ok)
+        if constexpr (kDeferred && kSearch == kSearchLdsCorner && !kStep && kMesh == 0 && kKind == kKindLean)
+            return {reinterpret_cast<const void *>(&corner::plain::trace_kernel<true, true, false, 0, false, false>),
+                    threads, true};
+        else
+            return {nullptr, 0, false};
+    } else if constexpr (kDeferred) {  // deferred leaves: the lean whole-walk corner kernel (render.h trace_variant)
         if constexpr (kSearch == kSearchLdsCorner && !kStep && kMesh == 0 && kKind == kKindLean)
             return {reinterpret_cast<const void *>(&corner::deferred::trace_kernel<true, true, false, 0, false, false>),
                     threads, true};
@@ -276,8 +296,8 @@ size_t trace_dyn_lds(const TraceParams &p, TraceVariant v) {
 }
 
 hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                        bool defer) {
-    const TraceVariant v = trace_variant(p, corner != nullptr, defer);
+                        bool defer, bool plain) {
+    const TraceVariant v = trace_variant(p, corner != nullptr, defer, plain);
     const TraceInstance &k = trace_instance(trace_index(v));
     if (k.fn == nullptr) return hipErrorInvalidValue;
     CornerParams cp{p, corner};  // (begins with the TraceParams: either kernel's argument block)
@@ -315,6 +335,8 @@ hipError_t trace_occupancy(int *blocks_per_cu, TraceVariant v, size_t lds_bytes)
     if (k.fn == nullptr) return hipErrorInvalidValue;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, (int)k.threads, lds_bytes);
 }
+
+bool trace_plain(TraceVariant v) { return v.plain && trace_instance(trace_index(v)).fn != nullptr; }
 
 int trace_leaf_defer(TraceVariant v) {
     return v.defer && trace_instance(trace_index(v)).fn != nullptr ? kLeafDeferC : 0;

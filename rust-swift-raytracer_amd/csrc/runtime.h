@@ -162,7 +162,8 @@ struct DeviceState {
     // lean twin the set-up's decisions were made with)
     int accum_blocks_per_cu[4][2] = {};
     int adapt_blocks_per_cu[4][2] = {};  // (kKindAdapt, likewise)
-    int defer_blocks_per_cu = 0;         // (the deferred-leaf lean corner instance)
+    int defer_blocks_per_cu = 0;         // (the deferred-leaf lean corner instance ...
+    bool plain_fits = false;             // ... and its plain twin keeps that many: it may run)
     int &occupancy(TraceVariant v) {
         if (v.defer) return defer_blocks_per_cu;
         return v.kind == kKindAdapt   ? adapt_blocks_per_cu[v.search][v.step]
@@ -190,6 +191,7 @@ struct DeviceState {
     size_t last_spp = 0;                                        // and its spp
     bool last_fused = false;                                    // it resolved in-kernel (no slab)
     int last_leaf_defer = 0;                                    // its walk's pending leaves per lane (rt_leaf_defer)
+    bool last_plain = false;                                    // it ran the plain instance (rt_trace_plain)
     ~DeviceState();
 };
 
@@ -393,6 +395,7 @@ void prepare_camera(WorldState &w, const CameraModel &cam, bool tree = false);
 
 long read_samples(WorldState &w, int device, float *out, size_t n);
 int leaf_defer(WorldState &w, int device);
+int trace_plain(WorldState &w, int device);
 // where the last frame launch's primary triangle lists were built (rt_primary_tri_lists)
 int primary_tri_lists(WorldState &w, int device);
 

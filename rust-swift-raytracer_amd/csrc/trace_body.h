@@ -134,10 +134,32 @@ __device__ __forceinline__ const Block &kernarg() {
 // flush when it exceeds the best_t of then: A/B slower, C2 +1.0 %)
 constexpr int kLeafDeferC = RT_LEAF_DEFER_C;
 static_assert(kLeafDeferC == 2 || kLeafDeferC == 3, "pending leaves per lane: 2 or 3");
+// kPlain (the deferred-leaf kernel only): the launch satisfies render.h
+// trace_plain_ok, so the loop's wave-uniform tests of launch constants are
+// decided here, at compile time: COUNTER seeds, 32-bit global jobs, u and v
+// through xdiv, primary sphere lists, gated walks, no ablation, the ring, a
+// tree of more than one node, both dividers in their general form and
+// plane-lane chunks only.  Each was an s_load -> s_waitcnt -> s_cmp ->
+// s_cbranch chain per iteration with the alternative's code behind it
+// (DESIGN.md 5.4 "scalar audit"; measured there and dropped: one copy of the
+// resolve with the slot's chunk selected into scalars, C2 +0.6 %, C3 +0.4 %,
+// and the refill's reads grouped under one wait, no change).  Values (depth,
+// camera, bounds, chunk, counters) are still read through kargs().  Every
+// test is written `kPlain || <the run-time test>`: the other instances
+// compile to the code they were.  RT_PLAIN_STEPS (diagnostic builds, the
+// per-step A/B): 1 the refill's tests, 2 the set-up, gate and ablation tests,
+// 4 the resolve's.
+#ifndef RT_PLAIN_STEPS
+#define RT_PLAIN_STEPS 7
+#endif
 template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner,
-          bool kAccum = false, bool kAdapt = false, int kDefer = 0>
+          bool kAccum = false, bool kAdapt = false, int kDefer = 0, bool kPlain = false>
 __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
     static_assert(!(kAccum && kAdapt), "an adaptive pass is an instance of its own");
+    static_assert(!kPlain || (kDefer != 0 && !kCount), "the plain instance: the lean deferred-leaf kernel");
+    constexpr bool kPlainRefill = kPlain && (RT_PLAIN_STEPS & 1) != 0;
+    constexpr bool kPlainWalk = kPlain && (RT_PLAIN_STEPS & 2) != 0;
+    constexpr bool kPlainResolve = kPlain && (RT_PLAIN_STEPS & 4) != 0;
     constexpr bool kWaveGuard = kMesh < 2;  // (exactdiv.h; the mesh kernels keep the per-lane fallbacks)
 #ifndef RT_COUNT_DEFER  // (diagnostic build: the counting corner instance with the deferred walk)
     static_assert(kDefer == 0 || (kCorner && !kCount && !kStep && !kSerial && kMesh == 0),
@@ -242,7 +264,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
     // Where a finished sample goes: the slab (slot = job) or, with the fused
     // resolve, the wave's ring (slot = ring offset = (k << ring_shift) + job -
     // rbase[k] for the chunk in ring slot k).  All wave-uniform.
-    const bool fused = p.ring != nullptr;
+    const bool fused = kPlainResolve || p.ring != nullptr;
     const uint32_t wave_id = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / kWave) +
                                                             threadIdx.x / kWave);
     float *const sbase = fused ? p.ring + (size_t)wave_id * (3u * kTraceRing << p.ring_shift)
@@ -340,10 +362,10 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     if (kBvh) {
                         spheres_big<kWaveGuard>(p, org, dir, best_t, best_i);
                         if (!kWalkState)
-                            node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
+                            node = kCorner ? sphere_corner_entry(sph_root, oct, kPlainWalk ? 2u : p.nnodes)
                                            : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
                         // (RT_AMD_ABLATE=1: timing-only diagnostic, results are wrong)
-                        phase = (p.ablate & 1u) ? kTriInit : kSph;
+                        phase = (!kPlainWalk && (p.ablate & 1u)) ? kTriInit : kSph;
                         if (!kMesh && bounce == 0 && (spl1 >> 16) != kSphListWalk) {
                             // primary ray: the pixel's candidate spheres instead of
                             // the walk (bvh.h PrimarySphereLists; same candidate
@@ -373,7 +395,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
             // iteration's walk: those lanes are shaded now and join the next
             // walk, so fewer walk segments run with lanes idle in them
             bool walk_now = true;
-            if (!kMesh && p.walk_min != 0) {
+            if (!kMesh && (kPlainWalk || p.walk_min != 0)) {
                 const uint32_t nwalk = (uint32_t)__popcll(__ballot(phase == kSph));
                 const uint32_t nother = (uint32_t)__popcll(__ballot(phase != kSph && !done));
                 walk_now = nwalk >= p.walk_min || nother == 0;
@@ -391,7 +413,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     // rule of the ray setup above, the same operations)
                     inv = f3(slab_rcp(dir.x), slab_rcp(dir.y), slab_rcp(dir.z));
                     oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
-                    node = kCorner ? sphere_corner_entry(sph_root, oct, p.nnodes)
+                    node = kCorner ? sphere_corner_entry(sph_root, oct, kPlainWalk ? 2u : p.nnodes)
                                    : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
                 }
                 if (kCorner) {
@@ -793,6 +815,9 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                         } else if (kAccum)
                             resolve_chunk<RT_PLANE_LANES(kMesh), true>(pc, sbase, pstride, k << pc.ring_shift,
                                                                        rbase[k], rlen[k], lane, atail().sums);
+                        else if (kPlainResolve)
+                            resolve_chunk<true, false, true>(pc, sbase, pstride, k << pc.ring_shift, rbase[k],
+                                                             rlen[k], lane);
                         else if (!(pc.ablate & 2u))
                             resolve_chunk<RT_PLANE_LANES(kMesh)>(pc, sbase, pstride, k << pc.ring_shift, rbase[k],
                                                   rlen[k], lane);
@@ -919,10 +944,10 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     const uint32_t pix = row * pc.width + col;
                     if (pc.gj32) gjob = pix * t.stride + (t.n0 + s);  // (W H S < 2^32)
                     else gjob = (uint64_t)pix * t.stride + (t.n0 + s);
-                } else if (!kSerial && pc.gj32) {
+                } else if (!kSerial && (kPlainRefill || pc.gj32)) {
                     // one rank, 32-bit global jobs (TraceParams::gj32)
-                    const uint32_t lp = fdiv(job, pc.div_spp);
-                    const uint32_t q = fdiv(lp, pc.div_width);
+                    const uint32_t lp = fdiv<kPlainRefill>(job, pc.div_spp);
+                    const uint32_t q = fdiv<kPlainRefill>(lp, pc.div_width);
                     col = lp - q * pc.width;
                     row = pc.height - 1u - (pc.slab_row0 + q);
                     gjob = job + pc.gj_c0 - q * pc.gj_2p;
@@ -937,7 +962,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     rng = serial_start(pc, job);
                     if (pc.mode == kRngSerialPixel) take = serial_pixel_job(pc, job);
                 } else {
-                    rng = (pc.mode == kRngReplay) ? pc.replay[gjob] : counter_seed(pc.seed, gjob);
+                    rng = (!kPlainRefill && pc.mode == kRngReplay) ? pc.replay[gjob] : counter_seed(pc.seed, gjob);
                 }
                 // common.rs:335-337: u drawn before v; camera.rs:84-89
                 // numerators are in [2^-32, 2^24]: exactdiv.h with the host's
@@ -945,7 +970,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                 const float un = draw_plus(rng, (float)col);
                 const float vn = draw_plus(rng, (float)row);
 #ifndef RT_NO_XDIV
-                const bool xd = pc.xdiv_uv != 0;
+                const bool xd = kPlainRefill || pc.xdiv_uv != 0;
 #else
                 const bool xd = false;
 #endif
@@ -957,10 +982,10 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                 const F3 llc = f3(pc.cam[3], pc.cam[4], pc.cam[5]);
                 vdir = ((llc + scale(h, u)) + scale(vv, v)) - org;  // normalised below
                 renorm = true;
-                if (kBvh && !kMesh && pc.spl != nullptr) {
+                if (kBvh && !kMesh && (kPlainRefill || pc.spl != nullptr)) {
                     // issued after the seed's (replay) load, so nothing waits on it
                     // before the ray's setup in the next iteration
-                    if (pc.ablate & 4u) {  // timing-only diagnostic: no record load
+                    if (!kPlainRefill && (pc.ablate & 4u)) {  // timing-only diagnostic: no record load
                         spl0 = 0;
                         spl1 = 0;
                     } else {

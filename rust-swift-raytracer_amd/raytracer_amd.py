@@ -37,6 +37,7 @@ EXPORTS = (
     "rt_accum_samples", "rt_accum_read", "rt_accum_reset", "rt_accum_free",
     "rt_adapt_default_options", "rt_adapt_enable", "rt_adapt_disable", "rt_adapt_active",
     "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active", "rt_leaf_defer",
+    "rt_trace_plain",
     "rt_camera_new_with_vertical_fov", "rt_camera_new_look_at", "rt_camera_from_floats",
     "rt_camera_translate", "rt_camera_free", "rt_primary_tri_lists", "rt_camera_record_builds",
     "rt_first_hit_default_options", "rt_first_hit", "rt_first_hit_device", "rt_first_hit_pick",
@@ -192,6 +193,9 @@ def lib(path=None):
         if hasattr(L, "rt_leaf_defer"):  # (an older build loaded for an A/B run has none)
             L.rt_leaf_defer.restype = C.c_int
             L.rt_leaf_defer.argtypes = [H, C.c_int]
+        if hasattr(L, "rt_trace_plain"):  # (likewise)
+            L.rt_trace_plain.restype = C.c_int
+            L.rt_trace_plain.argtypes = [H, C.c_int]
         if hasattr(L, "rt_camera_new_look_at"):  # (likewise)
             L.rt_camera_new_with_vertical_fov.restype = C.c_void_p
             L.rt_camera_new_with_vertical_fov.argtypes = [fp, C.c_float, C.c_float]
@@ -480,6 +484,14 @@ class World:
         n = self._L.rt_leaf_defer(self._h, device)
         if n < 0:
             raise RenderError(f"rt_leaf_defer failed ({n}): {self._L.rt_last_error().decode()}")
+        return n
+
+    def trace_plain(self, device=-1):
+        """rt_trace_plain: 1 when the last frame trace launch ran the plain instance
+        of the lean deferred-leaf kernel, 0 when it ran another instance."""
+        n = self._L.rt_trace_plain(self._h, device)
+        if n < 0:
+            raise RenderError(f"rt_trace_plain failed ({n}): {self._L.rt_last_error().decode()}")
         return n
 
     def render_device(self, width, height, out_ptr: int, stream_ptr: int = 0, spp=16, depth=8,
