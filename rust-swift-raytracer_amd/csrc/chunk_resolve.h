@@ -45,7 +45,7 @@ __device__ __forceinline__ void resolve_store(const TraceParams &p, uint32_t lp,
 // wide triangle walk (A/B on C5, 1-pixel chunks: 149.8 -> 148.1 ms, 2 VGPRs
 // spilled); the binary triangle walk keeps one lane per pixel
 #define RT_PLANE_LANES(mesh) ((mesh) < 2 || (mesh) == 3)
-// kAccum (accumulation passes, render.h AccumTail): a pixel's fold starts from
+// kAccum (accumulation passes, trace_body.h AccumTail): a pixel's fold starts from
 // its stored sum (sums: three planes of width * height floats, indexed like
 // p.out) instead of 0.0f and the new sum is stored back before gamma -- the
 // f32 fold of common.rs:333-341 stopped after a sample and continued from the
@@ -131,7 +131,7 @@ __device__ __forceinline__ void resolve_chunk(const TraceParams &p, const float 
     }
 }
 
-// The chunk resolve of an adaptive accumulation pass (render.h AdaptTail):
+// The chunk resolve of an adaptive accumulation pass (trace_body.h AdaptTail):
 // resolve_chunk<., kAccum> with every pixel index mapped through the pass's
 // list (launch-local pixel lp is frame pixel list[lp]) and a fourth fold per
 // pixel, q <- q + y y with y = (r + g) + b of each ring sample in sample order,

@@ -112,11 +112,11 @@ static int choose_lds_layout(const WorldState &w, DeviceState *d, size_t lds_cap
     const TriangleBVH &tw = w.tbvh;
     const uint32_t tw_depth = std::max<uint32_t>(1u, 3u * std::max(tw.wdepth, w.tcells.wdepth));
     bool wide = !tw.wnodes.empty() && env_u64("RT_AMD_TRI_WIDE", 1) != 0 &&
-                (size_t)tw_depth * trace_block_threads(trace_variant(kSearchLdsBox, false, 3, kKindLean)) * 2u <=
+                (size_t)tw_depth * trace_block_threads(TraceVariant{kSearchLdsBox, false, 3, kKindLean}) * 2u <=
                     64u * 1024u;
     int tri = wide ? 3 : trace_mesh_kind(w.packed.ntri > 0, !w.tbvh.nodes.empty());
     // the instance of kind c this scene runs with sphere search `search`
-    auto variant = [&](int search, int st, int c) { return trace_variant(search, st != 0, tri, c); };
+    auto variant = [&](int search, int st, int c) { return normalise_trace_variant({search, st != 0, tri, c}); };
     // the wide walk's stacks in LDS
     auto stack_lds = [&](TraceVariant v) -> size_t {
         return v.mesh == 3 ? (size_t)tw_depth * trace_block_threads(v) * 2u : 0u;
@@ -173,26 +173,20 @@ static int choose_lds_layout(const WorldState &w, DeviceState *d, size_t lds_cap
                         fits = false;
                     }
                 }
-            if (fits) {
-                // (the deferred-leaf lean instance, where the build has one)
-                const TraceVariant v = trace_variant(kSearchLdsCorner, false, tri, kKindLean, true);
-                if (trace_leaf_defer(v) != 0 &&
-                    (trace_occupancy(&d->occupancy(v), v, corner) != hipSuccess ||
-                     keeps_workgroups(v, corner, fits) != hipSuccess)) {
-                    (void)hipGetLastError();
-                    fits = false;
-                }
+            // (the deferred-leaf lean instance, where the build has one)
+            TraceVariant v = normalise_trace_variant({kSearchLdsCorner, false, tri, kKindLean, TraceLeaf::Deferred});
+            if (fits && trace_leaf_defer(v) != 0 &&
+                (trace_occupancy(&d->occupancy(v), v, corner) != hipSuccess ||
+                 keeps_workgroups(v, corner, fits) != hipSuccess)) {
+                (void)hipGetLastError();
+                fits = false;
             }
             if (fits) {
-                // (the plain twin runs only at the deferred instance's occupancy: the
-                // launch plans are made with that one)
-                TraceVariant v = trace_variant(kSearchLdsCorner, false, tri, kKindLean, true);
+                // (its plain twin's figure: DeviceState::plain_fits compares the two)
                 int blocks = 0;
-                v.plain = true;
-                if (trace_plain(v) && trace_occupancy(&blocks, v, corner) == hipSuccess)
-                    d->plain_fits = blocks == d->defer_blocks_per_cu;
-                else
-                    (void)hipGetLastError();
+                v.leaf = TraceLeaf::Plain;
+                if (trace_occupancy(&blocks, v, corner) == hipSuccess) d->occupancy(v) = blocks;
+                else (void)hipGetLastError();
             }
             if (fits) {
                 HIP_TRY(d->bvh_corner.upload(bv.corner));
@@ -247,9 +241,9 @@ static int choose_lds_layout(const WorldState &w, DeviceState *d, size_t lds_cap
         for (int st = 0; st < 2; ++st) {
             if (bpc)
                 for (int search : {kSearchBrute, kSearchGlobal, kSearchLdsBox})
-                    d->blocks_per_cu[search][c][st] = (int)bpc;
+                    d->occupancy(variant(search, st, c)) = (int)bpc;
             for (int search : {kSearchBrute, kSearchGlobal})
-                d->blocks_per_cu[search][c][st] = std::max(d->blocks_per_cu[search][c][st], 1);
+                d->occupancy(variant(search, st, c)) = std::max(d->occupancy(variant(search, st, c)), 1);
         }
     if (wide && !w.tbvh.nodes.empty()) d->tw_depth = tw_depth;
     return 0;

@@ -113,8 +113,8 @@ hipError_t replace_contents(DevBuf<T> &buf, const std::vector<U> &src, size_t mi
 // what check_frame_request found (negative: an error)
 enum { kFrameRender = 0, kFrameNothing = 1, kFrameSerial = 2 };
 
-// One frame launch's schedule for kernel kind k (0 lean, 1 counting):
-// workgroups, waves, jobs per queue pull (chunk) and job-queue partitions
+// One frame launch's schedule for a kernel instance: workgroups, waves, jobs
+// per queue pull (chunk) and job-queue partitions
 struct LaunchPlan { uint64_t blocks, nwaves, chunk, parts, block_threads; };
 
 // The values of a frame that are derived once, by the steps below in order
@@ -127,21 +127,20 @@ struct FrameValues {
     bool fused = false, replay = false;
     bool use_bvh = false;              // bind_sphere_search
     const uint4 *corner_img = nullptr; // the LDS tree as corner records (sphere-only frames), else box records
-    bool leaf_defer = false;           // ... walked with deferred leaf tests (render.h trace_variant)
-    bool plain = false;                // ... by the plain instance where a launch allows it (render.h trace_plain_ok)
+    TraceRequest want;                 // ... and what every launch asks for (render.h; kind: choose_kernel_instance)
     bool primary_lists = false;        // the frame's primary rays use candidate lists (spheres or triangles)
     bool use_tbvh = false;             // bind_triangle_search
     int ptl_where = 0;                 // rt_primary_tri_lists: 0 none, 1 host build, 2 device build
     float inv_spp = 0.0f;
-    bool timed = false, adapt = false; // choose_kernel_instance (timed: the caller wants stats)
-    int ctv = kKindLean;               // the kernel kind the frame runs ...
-    TraceVariant tv{};                 // ... and its instance
+    bool timed = false;                // choose_kernel_instance (timed: the caller wants stats)
+    TraceVariant tv{};                 // the instance the frame runs, the plain one apart: that is a launch's matter
     uint64_t waves_per_block = 0, full_blocks = 0, max_waves = 0;
 };
 
 // What enqueue_launches did, for the pending-stats record
 struct LaunchesDone {
     LaunchPlan lean_plan{0, 0, 0, 0, 0};  // the uncounted (timed) kernel's schedule of the last launch
+    TraceVariant variant{};               // ... and the instance it ran
     uint32_t launches = 0, waves = 0, nslab = 0;
     uint64_t samples = 0;
 };
@@ -240,7 +239,7 @@ void bind_scene(DeviceState *d, const CameraModel &cam, size_t width, size_t hei
     p.row_block = f.B; p.rank = o.rank; p.nranks = f.nranks;
 }
 
-// The sphere tree, its LDS layout (f.corner_img, f.leaf_defer) and the
+// The sphere tree, its LDS layout (f.corner_img, f.want) and the
 // primary sphere lists, built on the device or adopted from the host build
 int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
                        const RtRenderOptions &o, const SerialPass *sp, hipStream_t s, FrameValues &f,
@@ -255,11 +254,12 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
         const bool lds_on = env_u64("RT_AMD_LDS", 1) != 0;
         if (lds_on && sp == nullptr && d->corner_bytes > 0 && env_u64("RT_AMD_CORNER", 1) != 0)
             f.corner_img = d->bvh_corner.get();
+        f.want.corner = f.corner_img != nullptr;
         // (RT_AMD_LEAF_DEFER=0: the lean corner kernel tests leaves where it
         // enters them, for A/B runs and tests)
-        f.leaf_defer = f.corner_img != nullptr && env_u64("RT_AMD_LEAF_DEFER", 1) != 0;
+        f.want.defer = f.want.corner && env_u64("RT_AMD_LEAF_DEFER", 1) != 0;
         // (RT_AMD_PLAIN=0: every launch runs the generic instance, for A/B runs and tests)
-        f.plain = f.leaf_defer && d->plain_fits && env_u64("RT_AMD_PLAIN", 1) != 0;
+        f.want.plain = f.want.defer && d->plain_fits() && env_u64("RT_AMD_PLAIN", 1) != 0;
         p.use_lds = lds_on && (d->lds_bytes > 0 || f.corner_img != nullptr);
         // sphere-only scenes: primary rays test their pixel's candidates
         if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 && gpu_lists()) {
@@ -398,8 +398,15 @@ uint32_t alpha_byte(uint32_t nheld, float inv_spp) {
     return !(x > 0.0f) ? 0u : x >= 255.0f ? 255u : (uint32_t)x;  // saturating `as u8`
 }
 
-// The walk's refill and gate thresholds, the kernel instance the frame runs
-// (f.ctv, f.tv) with its occupancy, and the counters' buffer of a counted frame
+// The instance a frame's launches of kernel kind `kind` run, the plain one
+// apart (that takes the launch's chunk: enqueue_launches resolves it)
+TraceVariant frame_variant(const TraceParams &p, TraceRequest want, int kind) {
+    want.kind = kind, want.plain = false;
+    return resolve_trace_variant(p, want);
+}
+
+// The walk's refill and gate thresholds, the kernel kind and instance the frame runs
+// (f.want.kind, f.tv) with its occupancy, and the counters' buffer of a counted frame
 int choose_kernel_instance(DeviceState *d, const SerialPass *sp, const AccumPass *ap, hipStream_t s,
                            FrameValues &f, TraceParams &p) {
     // sliced walks pay off when walk lengths vary a lot: scenes with a triangle tree
@@ -419,13 +426,12 @@ int choose_kernel_instance(DeviceState *d, const SerialPass *sp, const AccumPass
     p.walk_min = (uint32_t)env_u64("RT_AMD_WALK_MIN", 65);  // sphere-only: walk when nothing else can advance
     p.tri_walk_min = (uint32_t)env_u64("RT_AMD_TRI_WALK_MIN", wide_frame ? 64 : 32);
     // (f.timed: HIP-event timing + counters need a host wait)
-    // launch_trace runs the counting kind iff p.stats (set below), the SERIAL instances for sp
+    // the counting kind iff p.stats (set below), the SERIAL instances for sp: launch_trace checks both
     // (an accumulation pass: its own kind, which has no counting twin -- a timed
     // pass gets its HIP-event times and schedule, the work counters stay 0)
     // (an adaptive pass: the accumulation kernels' twins that take their pixels from a list)
-    f.adapt = ap && ap->list != nullptr;
-    f.ctv = sp ? kKindSerial : f.adapt ? kKindAdapt : ap ? kKindAccum : f.timed ? kKindCounting : kKindLean;
-    f.tv = trace_variant(p, f.corner_img != nullptr, f.ctv, f.leaf_defer);
+    f.want.kind = sp ? kKindSerial : ap && ap->list ? kKindAdapt : ap ? kKindAccum : f.timed ? kKindCounting : kKindLean;
+    f.tv = frame_variant(p, f.want, f.want.kind);
     const TraceVariant tv = f.tv;
     if (ap && d->occupancy(tv) == 0) {
         int blocks = 0;
@@ -508,7 +514,7 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
     if (sp->mode == kRngSerialPixel) {
         // (job counters zeroed by serial_window_kernel, kPixtabParts of them)
         p.nparts = (uint32_t)std::min<uint64_t>(parts, kPixtabParts);
-        HIP_TRY(launch_trace(p, (uint32_t)blocks, s));
+        HIP_TRY(launch_trace(resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
     } else if (sp->mode == kRngSerialCoalesce) {
         // one workgroup per block of sp->R samples; the tree in LDS when it
         // fits beside the search's own arrays (64 KB per workgroup)
@@ -517,7 +523,7 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
                                        sp->dbg, s));
     } else {
         HIP_TRY(hipMemsetAsync(d->counter.get(), 0, parts * 128, s));
-        HIP_TRY(launch_trace(p, (uint32_t)blocks, s));
+        HIP_TRY(launch_trace(resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
     }
     HIP_TRY(hipEventRecord(d->done, s));
     d->done_stream = s;
@@ -525,10 +531,9 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
     return 0;
 }
 
-// The schedule of one frame launch of njobs jobs with kernel kind k
-LaunchPlan plan_launch(DeviceState *d, const TraceParams &p, const FrameValues &f, int k, uint64_t njobs) {
+// The schedule of one frame launch of njobs jobs with instance v
+LaunchPlan plan_launch(DeviceState *d, const TraceParams &p, const FrameValues &f, TraceVariant v, uint64_t njobs) {
     const uint32_t spp = f.spp;
-    const TraceVariant v = trace_variant(p, f.corner_img != nullptr, k, f.leaf_defer);
     const uint64_t wpb = trace_block_threads(v) / 64;
     const uint64_t jobs_per_block = wpb * 256;
     uint64_t blocks = std::min<uint64_t>((uint64_t)d->occupancy(v) * d->num_cus,
@@ -580,8 +585,10 @@ LaunchPlan plan_launch(DeviceState *d, const TraceParams &p, const FrameValues &
 int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_out, const AccumPass *ap,
                      hipStream_t s, const FrameValues &f, TraceParams &p, LaunchesDone &done) {
     const uint32_t spp = f.spp;
-    const bool fused = f.fused, timed = f.timed, adapt = f.adapt;
-    AccumTail tail{};
+    const bool fused = f.fused, timed = f.timed, adapt = f.want.kind == kKindAdapt;
+    TraceTail tail;
+    tail.corner = f.corner_img;
+    done.variant = f.tv;  // (a frame without a launch reports its own)
     if (ap) {
         AccumState &acc = *ap->acc;
         // the sums are the accumulator's own, not the device's scratch: a pass on
@@ -589,7 +596,8 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
         if (acc.done_stream && acc.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, acc.done, 0));
         // the first pass (after creation or a reset) starts every fold from 0.0f
         if (ap->n0 == 0) HIP_TRY(hipMemsetAsync(acc.sums.get(), 0, 3 * width * height * sizeof(float), s));
-        tail = AccumTail{acc.sums.get(), ap->n0, acc.stride};
+        tail.sums = acc.sums.get(), tail.n0 = ap->n0, tail.stride = acc.stride;
+        if (adapt) tail.sumsq = acc.sumsq.get();
         if (adapt && ap->n0 == 0) {
             // ... and an adaptive one with zero counts and every pixel listed
             HIP_TRY(hipMemsetAsync(acc.sumsq.get(), 0, width * height * sizeof(float), s));
@@ -623,13 +631,13 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
         p.gj32 = f.nranks == 1 && (uint64_t)width * height * spp < (1ull << 32) ? 1u : 0u;
         p.gj_c0 = (uint32_t)(((uint64_t)height - 1 - r0) * width * spp);
         p.gj_2p = (uint32_t)(2ull * width * spp);
-        // (accumulation: jobs at the accumulator's stride, render.h AccumTail)
+        // (accumulation: jobs at the accumulator's stride, render.h TraceTail)
         if (ap) p.gj32 = (uint64_t)width * height * ap->acc->stride < (1ull << 32) ? 1u : 0u;
         p.njobs = (uint32_t)njobs;
         p.npix = adapt ? (uint32_t)rows : (uint32_t)(rows * width);
         if (timed) HIP_TRY(hipEventRecord(ev3[0], s));
         if (njobs) {
-            const LaunchPlan lp = plan_launch(d, p, f, f.ctv, njobs);
+            const LaunchPlan lp = plan_launch(d, p, f, f.tv, njobs);
             const uint64_t blocks = lp.blocks, nwaves = lp.nwaves, chunk = lp.chunk, parts = lp.parts;
             p.chunk = (uint32_t)chunk;
             p.ring = nullptr;
@@ -648,21 +656,21 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             if (!d->cset_clean[d->cset]) HIP_TRY(hipMemsetAsync(cur, 0, parts * 128, s));
             p.job_counter = cur;
             p.job_counter_next = d->counter.get() + (size_t)(d->cset ^ 1u) * kMaxParts * 32;
-            if (adapt)
-                HIP_TRY(launch_trace_adapt(p, (uint32_t)blocks, s, f.corner_img,
-                                           AdaptTail{tail.sums, ap->acc->sumsq.get(), ap->list + r0, tail.n0, tail.stride}));
-            else if (ap) HIP_TRY(launch_trace_accum(p, (uint32_t)blocks, s, f.corner_img, tail));
-            else HIP_TRY(launch_trace(p, (uint32_t)blocks, s, f.corner_img, f.leaf_defer, f.plain));
-            d->last_leaf_defer = trace_leaf_defer(f.tv);
-            // (the launch's own parameters decide: chunk, ring and gj32 are set per launch)
-            d->last_plain = !ap && trace_plain(trace_variant(p, f.corner_img != nullptr, f.leaf_defer, f.plain));
+            // the launch's instance, resolved once (chunk, ring and gj32 are set per launch)
+            const TraceVariant v = resolve_trace_variant(p, f.want);
+            if (adapt) tail.list = ap->list + r0;
+            HIP_TRY(launch_trace(v, p, tail, (uint32_t)blocks, s));
+            done.variant = v;
+            d->last_leaf_defer = trace_leaf_defer(v);
+            d->last_plain = v.leaf == TraceLeaf::Plain;
             d->last_ptl = f.ptl_where;
             d->cset_clean[d->cset] = false;
             d->cset ^= 1u;
             d->cset_clean[d->cset] = true;
             p.job_counter = d->counter.get();
             p.job_counter_next = nullptr;
-            done.lean_plan = f.ctv == kKindLean || ap ? lp : plan_launch(d, p, f, kKindLean, njobs);
+            done.lean_plan =
+                f.want.kind != kKindCounting ? lp : plan_launch(d, p, f, frame_variant(p, f.want, kKindLean), njobs);
             d->last_jobs = fused ? 0 : njobs;
             d->last_spp = spp;
             d->last_fused = fused;  // rt_read_samples needs the slab
@@ -719,8 +727,9 @@ int queue_frame_stats(DeviceState *d, hipStream_t s, const FrameValues &f, const
     fx.launch_wsteps = p.wsteps;
     fx.launch_block_threads = (uint32_t)done.lean_plan.block_threads;
     fx.launch_blocks = (uint32_t)done.lean_plan.blocks;
-    fx.sphere_tree = (uint32_t)f.tv.search;
-    fx.sphere_tree_lds_bytes = f.tv.lds() ? (uint32_t)trace_lds_bytes(p, f.tv.search == kSearchLdsCorner) : 0u;
+    const TraceVariant v = done.variant;
+    fx.sphere_tree = (uint32_t)v.search;
+    fx.sphere_tree_lds_bytes = v.lds() ? (uint32_t)trace_lds_bytes(p, v.search == kSearchLdsCorner) : 0u;
     fx.nsph = d->nsph;
     fx.ntri = d->ntri;
     fx.nbig = d->nbig;

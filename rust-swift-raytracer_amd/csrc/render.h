@@ -208,56 +208,65 @@ RT_HOST_DEVICE inline uint32_t serial_lo(const SerialPred &M, uint32_t a, uint32
 // force (no triangle tree), 2 triangle trees (TraceParams::tnodes != 0)
 inline int trace_mesh_kind(bool triangles, bool tree) { return !triangles ? 0 : tree ? 2 : 1; }
 
-// One trace_kernel / corner::trace_kernel instance (render.hip trace_instance
-// spells each of them once).
+// One trace_kernel / corner::trace_kernel / accum:: / adapt::trace_kernel
+// instance (render.hip trace_instance_at spells each of them once).
 //   search: the sphere search (RtRenderStats::sphere_tree reports it)
 //   step:   the sliced-walk kernel (TraceParams::step)
 //   mesh:   trace_mesh_kind, or 3: triangle trees walked through the 4-wide
 //           image (TraceParams::tw_nodes)
 //   kind:   what the jobs are (kKindAccum: one pass of a progressive
-//           accumulation, launch_trace_accum; lean-like, no counters;
-//           kKindAdapt: its adaptive twin, launch_trace_adapt, whose pixels come
-//           from a list)
+//           accumulation, lean-like, no counters; kKindAdapt: its adaptive
+//           twin, whose pixels come from a list)
+//   leaf:   the corner walk tests a leaf where it enters it, or in shared leaf
+//           passes (DESIGN.md 5.2 "deferred leaves"), or so with the launch's
+//           constants compiled in (DESIGN.md 5.1 "the plain instance")
 enum : int { kSearchBrute = 0, kSearchGlobal = 1, kSearchLdsBox = 2, kSearchLdsCorner = 3 };
 enum : int { kKindLean = 0, kKindCounting = 1, kKindSerial = 2, kKindAccum = 3, kKindAdapt = 4 };
-//   defer:  the corner walk defers its leaf tests to shared leaf passes
-//           (DESIGN.md 5.2 "deferred leaves")
-//   plain:  the deferred-leaf kernel with the launch's constants compiled in
-//           (trace_plain_ok; DESIGN.md 5.1 "the plain instance")
+constexpr int kTraceKinds = 5;
+enum class TraceLeaf : int { Immediate = 0, Deferred = 1, Plain = 2 };
 struct TraceVariant {
     int search;
     bool step;
     int mesh;
     int kind;
-    bool defer = false;
-    bool plain = false;
-    bool lds() const { return search >= kSearchLdsBox; }
+    TraceLeaf leaf = TraceLeaf::Immediate;
+    constexpr bool lds() const { return search >= kSearchLdsBox; }
 };
-// The instance that serves a scene of family `mesh` (0-3) searched as `search`:
-// the SERIAL passes keep the binary triangle walk and the box records, and the
-// corner records exist for sphere-only scenes.  The one place these rules live.
-// defer: deferred leaf tests are wanted (RT_AMD_LEAF_DEFER, on by default).  Only
-// the lean whole-walk corner kernel has them: the counting kernel keeps the
-// immediate walk (its counters describe that walk), and so do the sliced
-// walks and the accumulation kinds.
-inline TraceVariant trace_variant(int search, bool step, int mesh, int kind, bool defer = false) {
-    if (kind == kKindSerial && mesh == 3) mesh = 2;
-    if (search == kSearchLdsCorner && (mesh != 0 || kind == kKindSerial)) search = kSearchLdsBox;
-    defer = defer && search == kSearchLdsCorner && !step && mesh == 0 && kind == kKindLean;
-    return TraceVariant{search, step, mesh, kind, defer};
+// The instance that serves what `want` describes.  The one place these rules
+// live: the SERIAL passes keep the binary triangle walk and the box records;
+// the corner records exist for sphere-only scenes; only the lean whole-walk
+// corner kernel has deferred leaf tests (asked for by any leaf but Immediate)
+// -- the counting kernel keeps the immediate walk its counters describe, and
+// so do the sliced walks and the accumulation kinds.  Never Plain: that is
+// decided per launch (resolve_trace_variant).
+constexpr TraceVariant normalise_trace_variant(TraceVariant want) {
+    TraceVariant v = want;
+    if (v.kind == kKindSerial && v.mesh == 3) v.mesh = 2;
+    if (v.search == kSearchLdsCorner && (v.mesh != 0 || v.kind == kKindSerial)) v.search = kSearchLdsBox;
+    const bool defer = want.leaf != TraceLeaf::Immediate && v.search == kSearchLdsCorner && !v.step && v.mesh == 0 &&
+                       v.kind == kKindLean;
+    v.leaf = defer ? TraceLeaf::Deferred : TraceLeaf::Immediate;
+    return v;
 }
-// ... and the one a launch with these parameters runs as kernel kind `kind`;
-// corner: the corner records are passed (launch_trace)
-inline TraceVariant trace_variant(const TraceParams &p, bool corner, int kind, bool defer = false) {
-    const int mesh = trace_mesh_kind(p.ntri != 0, p.tnodes != 0);
-    const int search = !p.nnodes ? kSearchBrute : !p.use_lds ? kSearchGlobal : corner ? kSearchLdsCorner : kSearchLdsBox;
-    return trace_variant(search, p.step != 0, mesh == 2 && p.tw_nodes != nullptr ? 3 : mesh, kind, defer);
+// A variant's place in the instance table: the (search, step, mesh, kind) grid,
+// then the deferred-leaf instance and its plain twin, which exist once each,
+// then kTraceNoKey, where every variant without an instance goes (it stays
+// empty).  trace_variant_at is the inverse.
+constexpr int kTraceGridKeys = 4 * 2 * 4 * kTraceKinds;
+constexpr int kTraceKeyDeferred = kTraceGridKeys, kTraceKeyPlain = kTraceGridKeys + 1;
+constexpr int kTraceNoKey = kTraceGridKeys + 2, kTraceKeys = kTraceGridKeys + 3;
+constexpr int trace_key(TraceVariant v) {
+    if (v.search < 0 || v.search > kSearchLdsCorner || v.mesh < 0 || v.mesh > 3 || v.kind < 0 || v.kind >= kTraceKinds)
+        return kTraceNoKey;
+    if (v.leaf == TraceLeaf::Immediate) return ((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind;
+    if (v.search != kSearchLdsCorner || v.step || v.mesh != 0 || v.kind != kKindLean) return kTraceNoKey;
+    return v.leaf == TraceLeaf::Deferred ? kTraceKeyDeferred : kTraceKeyPlain;
 }
-// Frames rendered without stats run a kind whose work counters compile away
-// (one VALU increment per node / sphere test / ray); SERIAL passes their own.
-inline TraceVariant trace_variant(const TraceParams &p, bool corner, bool defer) {
-    return trace_variant(p, corner, p.mode >= kRngSerialCount ? kKindSerial : p.stats ? kKindCounting : kKindLean,
-                         defer);
+constexpr TraceVariant trace_variant_at(int key) {
+    if (key == kTraceKeyDeferred || key == kTraceKeyPlain)
+        return {kSearchLdsCorner, false, 0, kKindLean, key == kTraceKeyPlain ? TraceLeaf::Plain : TraceLeaf::Deferred};
+    if (key < 0 || key >= kTraceGridKeys) return {-1, false, 0, 0};
+    return {key / (8 * kTraceKinds), key / (4 * kTraceKinds) % 2 != 0, key / kTraceKinds % 4, key % kTraceKinds};
 }
 
 // What the plain instance (trace_body's kPlain) takes for granted about its
@@ -270,56 +279,61 @@ inline bool trace_plain_ok(const TraceParams &p) {
            p.spl != nullptr && p.walk_min != 0 && p.ablate == 0 && p.nnodes > 1 && p.div_spp.one == 0 &&
            p.div_width.one == 0 && (p.spp & 3u) == 0 && p.chunk % p.spp == 0 && 3u * (p.chunk / p.spp) <= 64u;
 }
-// ... with plain: the plain instance is wanted (RT_AMD_PLAIN, on by default).
-// It exists for the deferred-leaf kernel alone, and only a launch that
-// satisfies trace_plain_ok runs it.
-inline TraceVariant trace_variant(const TraceParams &p, bool corner, bool defer, bool plain) {
-    TraceVariant v = trace_variant(p, corner, defer);
-    v.plain = plain && v.defer && trace_plain_ok(p);
+// What a caller asks of a launch, by name.  corner: the corner records are
+// there to stage.  kind: always stated, never inferred (launch_trace checks p
+// against it); frames rendered without stats run a kind whose work counters
+// compile away (one VALU increment per node / sphere test / ray).  defer, plain:
+// RT_AMD_LEAF_DEFER and RT_AMD_PLAIN, both on by default, want those instances.
+struct TraceRequest {
+    bool corner = false;
+    int kind = kKindLean;
+    bool defer = false, plain = false;
+};
+// ... and the instance that launch runs with parameters p.  The plain instance
+// exists for the deferred-leaf kernel alone, and only a launch that satisfies
+// trace_plain_ok runs it (so ask once chunk, ring and gj32 are set).
+inline TraceVariant resolve_trace_variant(const TraceParams &p, const TraceRequest &r) {
+    const int mesh = trace_mesh_kind(p.ntri != 0, p.tnodes != 0);
+    const int search = !p.nnodes ? kSearchBrute : !p.use_lds ? kSearchGlobal : r.corner ? kSearchLdsCorner : kSearchLdsBox;
+    TraceVariant v = normalise_trace_variant({search, p.step != 0, mesh == 2 && p.tw_nodes != nullptr ? 3 : mesh, r.kind,
+                                              r.defer ? TraceLeaf::Deferred : TraceLeaf::Immediate});
+    if (r.plain && v.leaf == TraceLeaf::Deferred && trace_plain_ok(p)) v.leaf = TraceLeaf::Plain;
     return v;
 }
 
-// corner (sphere-only frames with p.use_lds): the corner records (bvh.h
-// SphereBVH::corner, 8 uint4 per node) the workgroups stage instead of the box
-// records (the corner-record kernel instances; trace_corner_lds bytes each).
-// Runs instance trace_variant(p, corner != nullptr, defer, plain).
-hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream,
-                        const uint4 *corner = nullptr, bool defer = false, bool plain = false);
-// v is the plain instance and the build has it
-bool trace_plain(TraceVariant v);
-// Pending leaves per lane of instance v's deferred walk; 0: it tests leaves
-// where it enters them.
-int trace_leaf_defer(TraceVariant v);
-// One pass of a progressive accumulation: the frame launch p
-// (p.spp = the pass's samples per pixel n, fused resolve, one rank) as instance
-// trace_variant(p, corner != nullptr, kKindAccum).  Sample s of the pass at
-// reference (row, col) is global job (row W + col) stride + n0 + s (seed /
-// replay index; 32-bit arithmetic when p.gj32, which the host sets iff
-// W H stride < 2^32).  sums: three f32 planes of W H sums (R, G, B), indexed
-// like p.out: each pixel's fold starts from its stored sum and the new sum is
-// stored back before gamma (p.inv_spp and p.alpha_u8 are those of n0 + n samples).
-struct AccumTail {
-    float *sums;
-    uint32_t n0, stride;
-};
-hipError_t launch_trace_accum(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                              const AccumTail &tail);
-// One pass of an adaptive accumulation, instance
-// trace_variant(p, corner != nullptr, kKindAdapt): launch_trace_accum's pass
+// What a launch takes beside its TraceParams.  corner (sphere-only frames with
+// p.use_lds): the corner records (bvh.h SphereBVH::corner, 8 uint4 per node) the
+// corner search's workgroups stage, trace_corner_lds bytes each.  The rest is a pass's.
+// One pass of a progressive accumulation (kKindAccum): the frame
+// launch p (p.spp = the pass's samples per pixel n, fused resolve, one rank).
+// Sample s of the pass at reference (row, col) is global job (row W + col)
+// stride + n0 + s (seed / replay index; 32-bit arithmetic when p.gj32, which
+// the host sets iff W H stride < 2^32).  sums: three f32 planes of W H sums
+// (R, G, B), indexed like p.out: each pixel's fold starts from its stored sum
+// and the new sum is stored back before gamma (p.inv_spp and p.alpha_u8 are
+// those of n0 + n samples).
+// One pass of an adaptive accumulation (kKindAdapt): that pass
 // over the p.npix pixels of `list` only.  Launch-local pixel lp is frame pixel
 // list[lp] (index into p.out, top row first; p.slab_row0 = 0): its row, column,
 // global job and primary-list records derive from that, and the chunk resolve
 // maps through the list as well.  The resolve continues a fourth fold per
 // pixel, sumsq[pixel] <- sumsq + y y with y = (r + g) + b of each sample in
 // order (one rounded f32 operation each, no contraction).
-struct AdaptTail {
-    float *sums;
-    float *sumsq;
-    const uint32_t *list;
-    uint32_t n0, stride;
+struct TraceTail {
+    const uint4 *corner = nullptr;
+    float *sums = nullptr, *sumsq = nullptr;
+    const uint32_t *list = nullptr;
+    uint32_t n0 = 0, stride = 0;
 };
-hipError_t launch_trace_adapt(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                              const AdaptTail &tail);
+// The one launch of a trace kernel: instance v (resolve_trace_variant's) with
+// the argument block it takes, built from p and tail.  hipErrorInvalidValue:
+// no such instance, or p disagrees with v.kind -- counting iff p.stats, SERIAL iff
+// p.mode >= kRngSerialCount, a pass kind with p.ring and its tail's pointers set.
+hipError_t launch_trace(TraceVariant v, const TraceParams &p, const TraceTail &tail, uint32_t blocks,
+                        hipStream_t stream);
+// Pending leaves per lane of instance v's deferred walk; 0: it tests leaves
+// where it enters them.
+int trace_leaf_defer(TraceVariant v);
 // First-hit records (first_hit.hip): one lane per pixel of the
 // rectangle (x0, y0 from the top row, w x h, inside the p.width x p.height
 // frame) casts the frame's primary ray with its two draws replaced by su, sv

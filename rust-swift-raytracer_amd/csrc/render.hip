@@ -28,7 +28,7 @@
 // device code is in headers by concern, compiled here and nowhere else (in a
 // unit of their own the coalescing kernels come out as other code): this file
 // keeps the kernel entry points, the resolve kernel, the instance table and
-// the host launchers.
+// the host launchers (one for every trace kernel: launch_trace).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -51,11 +51,16 @@
 namespace rtamd {
 namespace {
 
+// Each entry point spells its trace_body configuration by field name, as a
+// local type Cfg (trace_body.h TraceConfig; a field left alone keeps its default).
 template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial = false>
 __global__ __launch_bounds__(trace_threads(kLds, kMesh, kSerial ? 2 : kCount ? 1 : 0))
 __attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, kSerial ? 2 : kCount ? 1 : 0), 8)))
 void trace_kernel(TraceParams p) {
-    trace_body<kBvh, kLds, kStep, kMesh, kCount, kSerial, false>(p, nullptr);
+    struct Cfg : TraceConfig {
+        constexpr Cfg() { bvh = kBvh, lds = kLds, step = kStep, mesh = kMesh, count = kCount, serial = kSerial; }
+    };
+    trace_body<Cfg>(p, nullptr);
 }
 
 // The sphere-only frame kernels over the corner records: instances of their
@@ -75,7 +80,10 @@ __global__ __launch_bounds__(trace_threads(true, 0, kCount ? 1 : 0))
 __attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(true, 0, kCount ? 1 : 0), 8)))
 void trace_kernel(CornerParams c) {
     static_assert(kBvh && kLds && kMesh == 0 && !kSerial, "corner records: sphere-only LDS frame kernels");
-    trace_body<true, true, kStep, 0, kCount, false, true>(c.p, c.image);
+    struct Cfg : TraceConfig {
+        constexpr Cfg() { bvh = lds = corner = true, step = kStep, count = kCount; }
+    };
+    trace_body<Cfg>(c.p, c.image);
 }
 // The lean whole-walk kernel with deferred leaf tests (trace_body's kDefer):
 // an instance of its own beside the immediate walk above, which stays the code
@@ -86,7 +94,10 @@ __global__ __launch_bounds__(trace_threads(true, 0, kCount ? 1 : 0))
 __attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(true, 0, kCount ? 1 : 0), 8)))
 void trace_kernel(CornerParams c) {
     static_assert(kBvh && kLds && !kStep && kMesh == 0 && !kSerial, "deferred leaves: whole corner walks");
-    trace_body<true, true, false, 0, kCount, false, true, false, false, kLeafDeferC>(c.p, c.image);
+    struct Cfg : TraceConfig {
+        constexpr Cfg() { bvh = lds = corner = true, count = kCount, defer = kLeafDeferC; }
+    };
+    trace_body<Cfg>(c.p, c.image);
 }
 }  // namespace deferred
 // The deferred-leaf kernel with the launch's constants compiled in
@@ -100,7 +111,10 @@ __global__ __launch_bounds__(trace_threads(true, 0, 0))
 __attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(true, 0, 0), 8)))
 void trace_kernel(CornerParams c) {
     static_assert(kBvh && kLds && !kStep && kMesh == 0 && !kCount && !kSerial, "plain: the lean deferred-leaf kernel");
-    trace_body<true, true, false, 0, false, false, true, false, false, kLeafDeferC, true>(c.p, c.image);
+    struct Cfg : TraceConfig {
+        constexpr Cfg() { bvh = lds = corner = plain = true, defer = kLeafDeferC; }
+    };
+    trace_body<Cfg>(c.p, c.image);
 }
 }  // namespace plain
 }  // namespace corner
@@ -117,7 +131,10 @@ __global__ __launch_bounds__(trace_threads(kLds, kMesh, 0))
 __attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, 0), 8)))
 void trace_kernel(AccumParams a) {
     static_assert(!kCorner || (kBvh && kLds && kMesh == 0), "corner records: sphere-only LDS kernels");
-    trace_body<kBvh, kLds, kStep, kMesh, false, false, kCorner, true>(a.p, a.image);
+    struct Cfg : TraceConfig {
+        constexpr Cfg() { bvh = kBvh, lds = kLds, step = kStep, mesh = kMesh, corner = kCorner, accum = true; }
+    };
+    trace_body<Cfg>(a.p, a.image);
 }
 }  // namespace accum
 
@@ -130,7 +147,10 @@ __global__ __launch_bounds__(trace_threads(kLds, kMesh, 0))
 __attribute__((amdgpu_waves_per_eu(trace_waves_per_eu(kLds, kMesh, 0), 8)))
 void trace_kernel(AdaptParams a) {
     static_assert(!kCorner || (kBvh && kLds && kMesh == 0), "corner records: sphere-only LDS kernels");
-    trace_body<kBvh, kLds, kStep, kMesh, false, false, kCorner, false, true>(a.p, a.image);
+    struct Cfg : TraceConfig {
+        constexpr Cfg() { bvh = kBvh, lds = kLds, step = kStep, mesh = kMesh, corner = kCorner, adapt = true; }
+    };
+    trace_body<Cfg>(a.p, a.image);
 }
 }  // namespace adapt
 
@@ -203,84 +223,56 @@ __global__ __launch_bounds__(kResolveWaves * 64) void resolve_kernel(
 
 // ------------------------------------------------------------ the instances
 // Every trace_kernel / corner::trace_kernel / accum:: / adapt::trace_kernel instance is
-// spelled here and nowhere else: launches, occupancy queries and the LDS opt-in
-// look it up by its TraceVariant (render.h).
+// spelled here and nowhere else, in one table by render.h trace_key: the launch,
+// the occupancy queries and the LDS opt-in look it up by its TraceVariant.
 struct TraceInstance {
     const void *fn;    // nullptr: no such instance
     uint32_t threads;  // per workgroup (the kernel's __launch_bounds__)
-    bool corner;       // takes CornerParams (kKindAccum: AccumParams, kKindAdapt: AdaptParams,
-                       // whatever the search)
 };
-constexpr int kTraceKinds = 5;
-constexpr int kTraceVariants = 4 * 2 * 4 * kTraceKinds * 2 * 2;  // search x step x mesh x kind x defer x plain
-constexpr int trace_index(TraceVariant v) {
-    return ((((v.search * 2 + v.step) * 4 + v.mesh) * kTraceKinds + v.kind) * 2 + v.defer) * 2 + v.plain;
+template <class Kernel>
+static TraceInstance instance_of(Kernel *kernel, uint32_t threads) {
+    return {reinterpret_cast<const void *>(kernel), threads};
 }
 
-// an accumulation pass's kernel (kAdapt: an adaptive pass's)
-template <bool kAdapt, bool kBvh, bool kLds, bool kStep, int kMesh, bool kCorner>
-static const void *pass_kernel() {
-    if constexpr (kAdapt) return reinterpret_cast<const void *>(&adapt::trace_kernel<kBvh, kLds, kStep, kMesh, kCorner>);
-    else return reinterpret_cast<const void *>(&accum::trace_kernel<kBvh, kLds, kStep, kMesh, kCorner>);
-}
-
-template <int kJ>
+// the instance of the variant with table key kKey
+template <int kKey>
 static TraceInstance trace_instance_at() {
-    constexpr int kI = kJ / 4;
-    constexpr bool kDeferred = kJ / 2 % 2 != 0, kPlain = kJ % 2 != 0;
-    constexpr int kSearch = kI / (8 * kTraceKinds), kMesh = kI / kTraceKinds % 4, kKind = kI % kTraceKinds;
-    constexpr bool kStep = kI / (4 * kTraceKinds) % 2 != 0, kCount = kKind == kKindCounting,
-                   kSerial = kKind == kKindSerial, kAccum = kKind == kKindAccum, kAdapt = kKind == kKindAdapt;
+    constexpr TraceVariant kV = trace_variant_at(kKey);
+    constexpr bool kBvh = kV.search != kSearchBrute, kLds = kV.lds(), kCorner = kV.search == kSearchLdsCorner,
+                   kStep = kV.step, kCount = kV.kind == kKindCounting, kSerial = kV.kind == kKindSerial,
+                   kAccum = kV.kind == kKindAccum, kAdapt = kV.kind == kKindAdapt;
     // (an accumulation pass runs at its lean twin's workgroup size)
-    constexpr uint32_t threads =
-        trace_threads(kSearch >= kSearchLdsBox, kMesh, kAccum || kAdapt ? (int)kKindLean : kKind);
-    if constexpr (kPlain) {  // the deferred-leaf kernel's plain twin (render.h trace_plain_ok)
-        if constexpr (kDeferred && kSearch == kSearchLdsCorner && !kStep && kMesh == 0 && kKind == kKindLean)
-            return {reinterpret_cast<const void *>(&corner::plain::trace_kernel<true, true, false, 0, false, false>),
-                    threads, true};
-        else
-            return {nullptr, 0, false};
-    } else if constexpr (kDeferred) {  // deferred leaves: the lean whole-walk corner kernel (render.h trace_variant)
-        if constexpr (kSearch == kSearchLdsCorner && !kStep && kMesh == 0 && kKind == kKindLean)
-            return {reinterpret_cast<const void *>(&corner::deferred::trace_kernel<true, true, false, 0, false, false>),
-                    threads, true};
-        else
-            return {nullptr, 0, false};
-    } else if constexpr (kSerial && kMesh == 3) {  // the SERIAL passes keep the binary triangle walk
-        return {nullptr, 0, false};
-    } else if constexpr ((kAccum || kAdapt) && kSearch != kSearchLdsCorner) {
-        return {pass_kernel<kAdapt, kSearch != kSearchBrute, kSearch == kSearchLdsBox, kStep, kMesh, false>(), threads,
-                true};
-    } else if constexpr ((kAccum || kAdapt) && kMesh == 0) {
-        return {pass_kernel<kAdapt, true, true, kStep, 0, true>(), threads, true};
-    } else if constexpr (kAccum || kAdapt) {
-        return {nullptr, 0, false};
-    } else if constexpr (kSearch != kSearchLdsCorner) {
-        return {reinterpret_cast<const void *>(
-                    &trace_kernel<kSearch != kSearchBrute, kSearch == kSearchLdsBox, kStep, kMesh, kCount, kSerial>),
-                threads, false};
+    constexpr uint32_t threads = trace_threads(kLds, kV.mesh, kAccum || kAdapt ? (int)kKindLean : kV.kind);
+    if constexpr (kV.leaf == TraceLeaf::Plain) {  // the deferred-leaf kernel's plain twin (render.h trace_plain_ok)
+        return instance_of(&corner::plain::trace_kernel<true, true, false, 0, false, false>, threads);
+    } else if constexpr (kV.leaf == TraceLeaf::Deferred) {  // deferred leaves: the lean whole-walk corner kernel
+        return instance_of(&corner::deferred::trace_kernel<true, true, false, 0, false, false>, threads);
+    } else if constexpr (kKey == kTraceNoKey || trace_key(normalise_trace_variant(kV)) != kKey) {
+        return {nullptr, 0};  // not its own normal form: another instance serves it (render.h)
+    } else if constexpr (kAdapt) {
+        return instance_of(&adapt::trace_kernel<kBvh, kLds, kStep, kV.mesh, kCorner>, threads);
+    } else if constexpr (kAccum) {
+        return instance_of(&accum::trace_kernel<kBvh, kLds, kStep, kV.mesh, kCorner>, threads);
+    } else if constexpr (!kCorner) {
+        return instance_of(&trace_kernel<kBvh, kLds, kStep, kV.mesh, kCount, kSerial>, threads);
 #ifdef RT_COUNT_DEFER
-    } else if constexpr (kMesh == 0 && kCount && !kStep) {  // diagnostic build: the deferred walk, counted
-        return {reinterpret_cast<const void *>(&corner::deferred::trace_kernel<true, true, false, 0, true, false>),
-                threads, true};
+    } else if constexpr (kCount && !kStep) {  // diagnostic build: the deferred walk, counted
+        return instance_of(&corner::deferred::trace_kernel<true, true, false, 0, true, false>, threads);
 #endif
-    } else if constexpr (kMesh == 0 && !kSerial) {  // corner records: the sphere-only frame kernels
-        return {reinterpret_cast<const void *>(&corner::trace_kernel<true, true, kStep, 0, kCount, false>), threads,
-                true};
-    } else {
-        return {nullptr, 0, false};
+    } else {  // corner records: the sphere-only frame kernels
+        return instance_of(&corner::trace_kernel<true, true, kStep, 0, kCount, false>, threads);
     }
 }
-template <int... kI>
-static const TraceInstance *trace_table(std::integer_sequence<int, kI...>) {
-    static const TraceInstance table[] = {trace_instance_at<kI>()...};
+template <int... kKey>
+static const TraceInstance *trace_table(std::integer_sequence<int, kKey...>) {
+    static const TraceInstance table[] = {trace_instance_at<kKey>()...};
     return table;
 }
-static const TraceInstance &trace_instance(int index) {
-    return trace_table(std::make_integer_sequence<int, kTraceVariants>{})[index];
+static const TraceInstance &trace_instance(TraceVariant v) {
+    return trace_table(std::make_integer_sequence<int, kTraceKeys>{})[trace_key(v)];
 }
 
-uint32_t trace_block_threads(TraceVariant v) { return trace_instance(trace_index(v)).threads; }
+uint32_t trace_block_threads(TraceVariant v) { return trace_instance(v).threads; }
 
 size_t trace_lds_bytes(const TraceParams &p, bool corner) {
     // (shading records in global memory instead, which would allow 8 waves per
@@ -295,58 +287,49 @@ size_t trace_dyn_lds(const TraceParams &p, TraceVariant v) {
     return tree + (v.mesh == 3 ? (size_t)p.tw_depth * trace_block_threads(v) * 2u : 0u);
 }
 
-hipError_t launch_trace(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                        bool defer, bool plain) {
-    const TraceVariant v = trace_variant(p, corner != nullptr, defer, plain);
-    const TraceInstance &k = trace_instance(trace_index(v));
-    if (k.fn == nullptr) return hipErrorInvalidValue;
-    CornerParams cp{p, corner};  // (begins with the TraceParams: either kernel's argument block)
-    void *args[] = {k.corner ? (void *)&cp : (void *)&cp.p};
-    return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
-}
-
-// One pass of kind kKindAccum / kKindAdapt; Block: its argument block.
-// tail_ok: the tail's pointers are all set.
-template <class Block, class Tail>
-static hipError_t launch_trace_pass(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                                    int kind, const Tail &tail, bool tail_ok) {
-    const TraceVariant v = trace_variant(p, corner != nullptr, kind);
-    const TraceInstance &k = trace_instance(trace_index(v));
-    // (the passes resolve in-kernel: without a ring the samples would go to the slab)
-    if (k.fn == nullptr || p.ring == nullptr || !tail_ok) return hipErrorInvalidValue;
-    Block ap{p, v.search == kSearchLdsCorner ? corner : nullptr, tail};
-    void *args[] = {(void *)&ap};
-    return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
-}
-
-hipError_t launch_trace_accum(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                              const AccumTail &tail) {
-    return launch_trace_pass<AccumParams>(p, blocks, stream, corner, kKindAccum, tail, tail.sums != nullptr);
-}
-
-hipError_t launch_trace_adapt(const TraceParams &p, uint32_t blocks, hipStream_t stream, const uint4 *corner,
-                              const AdaptTail &tail) {
-    return launch_trace_pass<AdaptParams>(p, blocks, stream, corner, kKindAdapt, tail,
-                                          tail.sums != nullptr && tail.sumsq != nullptr && tail.list != nullptr);
+hipError_t launch_trace(TraceVariant v, const TraceParams &p, const TraceTail &tail, uint32_t blocks,
+                        hipStream_t stream) {
+    const TraceInstance &k = trace_instance(v);
+    if (k.fn == nullptr || (v.kind == kKindCounting) != (p.stats != nullptr) ||
+        (v.kind == kKindSerial) != (p.mode >= kRngSerialCount))
+        return hipErrorInvalidValue;
+    const uint4 *image = v.search == kSearchLdsCorner ? tail.corner : nullptr;
+    auto launch = [&](void *block) {
+        void *args[] = {block};
+        return hipLaunchKernel(k.fn, dim3(blocks), dim3(k.threads), args, trace_dyn_lds(p, v), stream);
+    };
+    if (v.kind == kKindAccum || v.kind == kKindAdapt) {
+        // (the passes resolve in-kernel: without a ring the samples would go to the slab)
+        if (p.ring == nullptr || tail.sums == nullptr) return hipErrorInvalidValue;
+        if (v.kind == kKindAccum) {
+            AccumParams block{p, image, AccumTail{tail.sums, tail.n0, tail.stride}};
+            return launch(&block);
+        }
+        if (tail.sumsq == nullptr || tail.list == nullptr) return hipErrorInvalidValue;
+        AdaptParams block{p, image, AdaptTail{tail.sums, tail.sumsq, tail.list, tail.n0, tail.stride}};
+        return launch(&block);
+    }
+    CornerParams block{p, image};  // (begins with the TraceParams: either frame kernel's argument block)
+    return launch(&block);
 }
 
 hipError_t trace_occupancy(int *blocks_per_cu, TraceVariant v, size_t lds_bytes) {
-    const TraceInstance &k = trace_instance(trace_index(v));
+    const TraceInstance &k = trace_instance(v);
     if (k.fn == nullptr) return hipErrorInvalidValue;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, (int)k.threads, lds_bytes);
 }
 
-bool trace_plain(TraceVariant v) { return v.plain && trace_instance(trace_index(v)).fn != nullptr; }
-
 int trace_leaf_defer(TraceVariant v) {
-    return v.defer && trace_instance(trace_index(v)).fn != nullptr ? kLeafDeferC : 0;
+    return v.leaf != TraceLeaf::Immediate && trace_instance(v).fn != nullptr ? kLeafDeferC : 0;
 }
 
 hipError_t trace_lds_opt_in() {
     hipError_t e = hipSuccess;
-    for (int i = trace_index(TraceVariant{kSearchLdsBox, false, 0, 0}); i < kTraceVariants && e == hipSuccess; ++i)
-        if (trace_instance(i).fn != nullptr)
-            e = hipFuncSetAttribute(trace_instance(i).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+    for (int key = 0; key < kTraceKeys && e == hipSuccess; ++key) {
+        const TraceVariant v = trace_variant_at(key);
+        if (v.lds() && trace_instance(v).fn != nullptr)
+            e = hipFuncSetAttribute(trace_instance(v).fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+    }
     return e;
 }
 

@@ -153,22 +153,22 @@ struct DeviceState {
     uint32_t cset = 0;              // the set the next frame launch uses ...
     bool cset_clean[2] = {false, false};  // ... and whether each set is known to be zero
     DevBuf<unsigned long long> stats;                           // per-wave counter records
-    // resident workgroups per CU of the scene's kernel instances (render.h
-    // TraceVariant), [search][kind][step], queried once at device setup for the
-    // scene's family (the corner search: frame kinds only)
-    int blocks_per_cu[4][3][2] = {};
-    // (the accumulation kind: queried by the first pass that runs an instance,
-    // 0 until then; same workgroup size, LDS request and waves per SIMD as the
-    // lean twin the set-up's decisions were made with)
-    int accum_blocks_per_cu[4][2] = {};
-    int adapt_blocks_per_cu[4][2] = {};  // (kKindAdapt, likewise)
-    int defer_blocks_per_cu = 0;         // (the deferred-leaf lean corner instance ...
-    bool plain_fits = false;             // ... and its plain twin keeps that many: it may run)
+    // resident workgroups per CU of the scene's kernel instances, by render.h
+    // trace_key less the mesh: a device holds one scene, whose frames all plan
+    // with its family's figures (a RT_ACCEL_BRUTE frame too).  The frame kinds
+    // and the two deferred-leaf instances are queried once at device set-up (the
+    // corner search: lean and counting only), the accumulation kinds by the
+    // first pass that runs an instance, 0 until then (same workgroup size, LDS
+    // request and waves per SIMD as the lean twin the set-up decided with).
+    // A variant without an instance: kTraceNoKey's slot, which stays 0.
+    int blocks_per_cu[kTraceKeys] = {};
     int &occupancy(TraceVariant v) {
-        if (v.defer) return defer_blocks_per_cu;
-        return v.kind == kKindAdapt   ? adapt_blocks_per_cu[v.search][v.step]
-               : v.kind == kKindAccum ? accum_blocks_per_cu[v.search][v.step]
-                                      : blocks_per_cu[v.search][v.kind][v.step];
+        v.mesh = 0;
+        return blocks_per_cu[trace_key(v)];
+    }
+    // the plain instance may run: it keeps the deferred-leaf instance's workgroups, which the launch plans use
+    bool plain_fits() const {
+        return blocks_per_cu[kTraceKeyPlain] != 0 && blocks_per_cu[kTraceKeyPlain] == blocks_per_cu[kTraceKeyDeferred];
     }
     int num_cus = 0;
     // a counted frame's timing events (3 per launch: start, trace end, resolve

@@ -93,16 +93,27 @@ constexpr int trace_waves_per_eu(bool lds, int mesh, int kind) {
 // The accumulation kernels' argument block: it begins with the TraceParams
 // (kargs() re-reads them from offset 0; TraceParams itself gets no field, its
 // offsets are those the frame kernels' kernarg loads were tuned with), then
-// the corner image (nullptr for the other searches) and the tail.
+// the corner image (nullptr for the other searches) and the tail (render.h
+// TraceTail's fields for this kind).
+struct AccumTail {
+    float *sums;
+    uint32_t n0, stride;
+};
 struct AccumParams {
     TraceParams p;
     const uint4 *image;
     AccumTail tail;
 };
 // kAdapt: one pass of an adaptive accumulation (adapt::trace_kernel below):
-// the pass's pixels are those of a list (render.h AdaptTail).  The refill maps
+// the pass's pixels are those of a list (render.h TraceTail).  The refill maps
 // the job's launch-local pixel through it, and so does the chunk resolve
 // (resolve_chunk_adapt); nothing else changes.
+struct AdaptTail {
+    float *sums;
+    float *sumsq;
+    const uint32_t *list;
+    uint32_t n0, stride;
+};
 struct AdaptParams {
     TraceParams p;
     const uint4 *image;
@@ -152,9 +163,22 @@ static_assert(kLeafDeferC == 2 || kLeafDeferC == 3, "pending leaves per lane: 2 
 #ifndef RT_PLAIN_STEPS
 #define RT_PLAIN_STEPS 7
 #endif
-template <bool kBvh, bool kLds, bool kStep, int kMesh, bool kCount, bool kSerial, bool kCorner,
-          bool kAccum = false, bool kAdapt = false, int kDefer = 0, bool kPlain = false>
+// One instance's configuration: every k... above by name.  trace_body takes a
+// type Cfg derived from it whose constexpr default constructor sets the
+// fields (each kernel entry point in render.hip spells one, field by field).
+struct TraceConfig {
+    bool bvh = false, lds = false, step = false;
+    int mesh = 0;
+    bool count = false, serial = false, corner = false, accum = false, adapt = false;
+    int defer = 0;
+    bool plain = false;
+};
+template <class Cfg>
 __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
+    constexpr TraceConfig kCfg = Cfg();
+    constexpr bool kBvh = kCfg.bvh, kLds = kCfg.lds, kStep = kCfg.step, kCount = kCfg.count, kSerial = kCfg.serial;
+    constexpr bool kCorner = kCfg.corner, kAccum = kCfg.accum, kAdapt = kCfg.adapt, kPlain = kCfg.plain;
+    constexpr int kMesh = kCfg.mesh, kDefer = kCfg.defer;
     static_assert(!(kAccum && kAdapt), "an adaptive pass is an instance of its own");
     static_assert(!kPlain || (kDefer != 0 && !kCount), "the plain instance: the lean deferred-leaf kernel");
     constexpr bool kPlainRefill = kPlain && (RT_PLAIN_STEPS & 1) != 0;
@@ -422,7 +446,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     F3 nn, nf;
                     sphere_corner_slabs(org, inv, sph_inflation(p, bnd, best_t), oct, nn, nf);
                     const uint32_t offn = sph_root + 16u * oct, offf = sph_root + 112u - 16u * oct;
-                    if (kDefer != 0) {
+                    if constexpr (kDefer != 0) {  // (constexpr: kDefer - 1 below is a shift count)
                         // Deferred leaves: a lane that enters a leaf records it
                         // and walks on; the walking lanes test their recorded
                         // leaves together once one of them holds kDefer, and

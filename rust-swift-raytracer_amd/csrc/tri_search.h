@@ -261,7 +261,7 @@ __device__ __forceinline__ void tri_primary_list(const TraceParams &p, uint32_t 
         tri_record(p.cam_tris + 4u * p.ptl_items[j], org, dir, best_t, tri_t, tri_i, tri_in);
 }
 
-// The same for an adaptive accumulation pass (render.h AdaptTail): the job's
+// The same for an adaptive accumulation pass (trace_body.h AdaptTail): the job's
 // launch-local pixel is frame pixel list[lp] (top row first).
 __device__ __forceinline__ void tri_primary_list_adapt(const TraceParams &p, const uint32_t *list, uint32_t job,
                                                        F3 org, F3 dir, float best_t, float &tri_t, int &tri_i,
