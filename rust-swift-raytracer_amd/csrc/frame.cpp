@@ -258,8 +258,9 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
         // (RT_AMD_LEAF_DEFER=0: the lean corner kernel tests leaves where it
         // enters them, for A/B runs and tests)
         f.want.defer = f.want.corner && env_u64("RT_AMD_LEAF_DEFER", 1) != 0;
-        // (RT_AMD_PLAIN=0: every launch runs the generic instance, for A/B runs and tests)
-        f.want.plain = f.want.defer && d->plain_fits() && env_u64("RT_AMD_PLAIN", 1) != 0;
+        // (RT_AMD_PLAIN=0: every launch runs the generic instance, for A/B runs and tests;
+        // so does a frame of depth <= 0: the plain instance ends a path after a hit)
+        f.want.plain = f.want.defer && d->plain_fits() && p.depth >= 1 && env_u64("RT_AMD_PLAIN", 1) != 0;
         p.use_lds = lds_on && (d->lds_bytes > 0 || f.corner_img != nullptr);
         // sphere-only scenes: primary rays test their pixel's candidates
         if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 && gpu_lists()) {

@@ -273,7 +273,9 @@ constexpr TraceVariant trace_variant_at(int key) {
 // launch; p as launch_trace gets it, every field set.  The one place this
 // rule lives: a launch that fails any line runs the instance it ran before.
 // Every chunk then has the plane-lane resolve's shape (chunk_resolve.h): a
-// partition's last chunk is shorter than p.chunk, never longer.
+// partition's last chunk is shorter than p.chunk, never longer.  (One more
+// thing the instance takes for granted is a frame's, not a launch's, and is
+// tested where the frame states its request: TraceRequest::plain, depth >= 1.)
 inline bool trace_plain_ok(const TraceParams &p) {
     return p.mode == kRngCounter && p.stats == nullptr && p.ring != nullptr && p.gj32 != 0 && p.xdiv_uv != 0 &&
            p.spl != nullptr && p.walk_min != 0 && p.ablate == 0 && p.nnodes > 1 && p.div_spp.one == 0 &&
@@ -284,6 +286,9 @@ inline bool trace_plain_ok(const TraceParams &p) {
 // against it); frames rendered without stats run a kind whose work counters
 // compile away (one VALU increment per node / sphere test / ray).  defer, plain:
 // RT_AMD_LEAF_DEFER and RT_AMD_PLAIN, both on by default, want those instances.
+// plain is asked only by a frame of depth >= 1: the plain instance tests the
+// depth where a path scatters, after its first hit, and a frame whose bounce 0
+// is already exhausted is black without one.
 struct TraceRequest {
     bool corner = false;
     int kind = kKindLean;

@@ -134,9 +134,23 @@ __device__ __forceinline__ float sph_inflation(const TraceParams &p, SphBound b,
     return fminf(kErrK * s, (kErrKq * s) * (s * p.bvh_inv_rmin)) + b.e_abs;
 }
 
-template <bool kWaveGuard>
+// kPeel (the plain instance): the first big sphere's record and id are read
+// at once and whatever nbig is -- both arrays hold an entry even when no sphere
+// is big (device_state.cpp) -- so one wait covers them and the count; the loop
+// takes the others.
+template <bool kWaveGuard, bool kPeel = false>
 __device__ __forceinline__ void spheres_big(const TraceParams &p, F3 org, F3 dir, float &best_t,
                                             int &best_i) {
+    if constexpr (kPeel) {
+        const uint32_t n = p.nbig;
+        const float4 S0 = uniform_load(p.big_hot, 0);
+        const int id0 = (int)uniform_load_u32(p.big_id, 0);
+        if (n != 0u) sphere_candidate<kWaveGuard>(S0, org, dir, id0, best_t, best_i);
+        for (uint32_t k = 1; k < n; ++k)
+            sphere_candidate<kWaveGuard>(uniform_load(p.big_hot, k), org, dir, (int)uniform_load_u32(p.big_id, k),
+                                         best_t, best_i);
+        return;
+    }
     for (uint32_t k = 0; k < p.nbig; ++k) {
         // (both scalar loads: a vector load here made the ray setup wait on
         // every outstanding vector memory op, vmcnt(0))

@@ -160,9 +160,32 @@ static_assert(kLeafDeferC == 2 || kLeafDeferC == 3, "pending leaves per lane: 2 
 // compile to the code they were.  RT_PLAIN_STEPS (diagnostic builds, the
 // per-step A/B): 1 the refill's tests, 2 the set-up, gate and ablation tests,
 // 4 the resolve's.
+// The instance's shading paths (DESIGN.md 5.1 "the shading block"; a frame asks
+// for the instance only with depth >= 1, render.h TraceRequest), bits of the same macro: 8 a path ends in the
+// shading block and nowhere else -- the depth test sits where ++bounce is and
+// the sample store inside the block, so the set-up has no depth chain and the
+// colour no default; 16 a shading lane is sky or sphere (kMesh == 0: no
+// triangle can win), so the sphere's records have no defaults either; 32 the
+// first big sphere's record and id are read together, unconditionally (both
+// arrays hold an entry even when there is no big sphere); 64 the sample store
+// takes the wave's base and a 32-bit byte offset per lane.
 #ifndef RT_PLAIN_STEPS
-#define RT_PLAIN_STEPS 7
+#define RT_PLAIN_STEPS 127
 #endif
+// The plain instance's sample store (RT_PLAIN_STEPS 64): the ring holds
+// 3 kTraceRing << ring_shift floats per wave, so a lane's byte offset into it
+// fits 32 bits.  The three stores take the wave's one scalar base and a per-lane
+// offset, the plane stride added per plane (three scalar bases cost 5 more SGPR
+// spills in the instance).
+__device__ __forceinline__ void store_planes(float *sbase, uint32_t pstride, uint32_t slot, float r, float g,
+                                             float b) {
+    char *const base = reinterpret_cast<char *>(sbase);
+    const uint32_t pb = pstride << 2;
+    const uint32_t off = slot << 2;
+    *reinterpret_cast<float *>(base + (size_t)off) = r;
+    *reinterpret_cast<float *>(base + (size_t)(off + pb)) = g;
+    *reinterpret_cast<float *>(base + (size_t)(off + 2u * pb)) = b;
+}
 // One instance's configuration: every k... above by name.  trace_body takes a
 // type Cfg derived from it whose constexpr default constructor sets the
 // fields (each kernel entry point in render.hip spells one, field by field).
@@ -184,6 +207,11 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
     constexpr bool kPlainRefill = kPlain && (RT_PLAIN_STEPS & 1) != 0;
     constexpr bool kPlainWalk = kPlain && (RT_PLAIN_STEPS & 2) != 0;
     constexpr bool kPlainResolve = kPlain && (RT_PLAIN_STEPS & 4) != 0;
+    constexpr bool kPlainEnd = kPlain && (RT_PLAIN_STEPS & 8) != 0;
+    constexpr bool kPlainShade = kPlain && (RT_PLAIN_STEPS & 16) != 0;
+    constexpr bool kPlainBig = kPlain && (RT_PLAIN_STEPS & 32) != 0;
+    constexpr bool kPlainStore = kPlain && kPlainResolve && (RT_PLAIN_STEPS & 64) != 0;
+    static_assert(!kPlainShade || kCfg.mesh == 0, "two kinds of shading lane: the sphere-only kernels");
     constexpr bool kWaveGuard = kMesh < 2;  // (exactdiv.h; the mesh kernels keep the per-lane fallbacks)
 #ifndef RT_COUNT_DEFER  // (diagnostic build: the counting corner instance with the deferred walk)
     static_assert(kDefer == 0 || (kCorner && !kCount && !kStep && !kSerial && kMesh == 0),
@@ -364,7 +392,8 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
             float out_r = 0.0f, out_g = 0.0f, out_b = 0.0f;
             if (phase == kSetup) {
                 const TraceParams &p = kargs();  // (ray setup: see kargs)
-                if ((int32_t)bounce >= p.depth) {
+                // (kPlainEnd: a path that reaches the depth ends where ++bounce was, below)
+                if (!kPlainEnd && (int32_t)bounce >= p.depth) {
                     done = true;  // depth exhausted -> (0, 0, 0) (common.rs:284)
                 } else {
                     ++rays;
@@ -384,7 +413,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     best_t = __builtin_inff();
                     best_i = -1;
                     if (kBvh) {
-                        spheres_big<kWaveGuard>(p, org, dir, best_t, best_i);
+                        spheres_big<kWaveGuard, kPlainBig>(p, org, dir, best_t, best_i);
                         if (!kWalkState)
                             node = kCorner ? sphere_corner_entry(sph_root, oct, kPlainWalk ? 2u : p.nnodes)
                                            : sphere_walk_entry<kLds>(sph_root, oct, p.nnodes);
@@ -690,20 +719,32 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                 // missed ray re-normalises its direction (common.rs:277), a
                 // sphere hit normalises (pos - c) / r (common.rs:95), so the
                 // wave runs one copy of the sqrt / divide sequence, not two
-                const bool sky = tri_i < 0 && best_i < 0;
-                const bool sph = tri_i < 0 && best_i >= 0;
-                F3 un = dir, spos = dir;
-                float4 SS = make_float4(0.0f, 0.0f, 0.0f, 0.0f), SM = SS;
-                uint32_t skind = 0;
+                // (kPlainShade: no triangle wins, a lane is sky or sphere; the
+                // sphere's values are then set on every path that reads them
+                // and get no default)
+                const bool sky = kPlainShade ? best_i < 0 : tri_i < 0 && best_i < 0;
+                const bool sph = kPlainShade ? !sky : tri_i < 0 && best_i >= 0;
+                F3 un = dir, spos;
+                float4 SS, SM;
+                uint32_t skind;
+                if (!kPlainShade) {
+                    spos = dir;
+                    SS = SM = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    skind = 0;
+                }
                 if (sph) {
                     // one round trip: centre/radius, colour/param and kind together
                     SS = view.shade[2 * best_i];
                     SM = view.shade[2 * best_i + 1];
                     skind = view.kinds[best_i];
-                    spos = org + scale(dir, best_t);
+                    // (kPlainShade: the hit point replaces the origin here.  A
+                    // sphere lane either scatters from it or ends, and a lane
+                    // that ended reads no origin before its refill sets one)
+                    if (kPlainShade) spos = org = org + scale(dir, best_t);
+                    else spos = org + scale(dir, best_t);
                     un = divide_by<kWaveGuard>(spos - f3(SS.x, SS.y, SS.z), SS.w);
                 }
-                if (sky || sph) un = unit<kWaveGuard>(un);
+                if (kPlainShade || sky || sph) un = unit<kWaveGuard>(un);
                 if (sky) {
                     // background (common.rs:276-281): re-normalise, lerp to sky blue
                     const float t = 0.5f * (un.y + 1.0f);
@@ -716,7 +757,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     F3 pos, nrm;
                     uint32_t kind;
                     float cr, cg, cb, param;
-                    if (tri_i >= 0) {  // a triangle wins a tie against a sphere
+                    if (!kPlainShade && tri_i >= 0) {  // a triangle wins a tie against a sphere
                         pos = org + scale(dir, tri_t);
                         const float4 *g = p.tri_geo + 4u * (uint32_t)tri_i;
                         const float4 A = g[0], Nn = g[3];
@@ -726,7 +767,7 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                         cr = m[1]; cg = m[2]; cb = m[3]; param = m[4];
                     } else {
                         kind = skind;
-                        pos = spos;
+                        pos = kPlainShade ? org : spos;
                         nrm = un;  // common.rs:95, normalised above
                         cr = SM.x; cg = SM.y; cb = SM.z; param = SM.w;
                     }
@@ -760,7 +801,9 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                     } else {  // Emission (materials.rs:100-102)
                         next = false;
                     }
-                    if (next) {
+                    // (kPlainEnd: the scattered ray would be bounce + 1, which the
+                    // set-up's depth test turned into (0, 0, 0), common.rs:284)
+                    if (next && !(kPlainEnd && (int32_t)(bounce + 1u) >= p.depth)) {
                         thr_r = thr_r * cr;
                         thr_g = thr_g * cg;
                         thr_b = thr_b * cb;
@@ -772,16 +815,31 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                             renorm = true;
                         }
                         ++bounce;
-                    } else {  // common.rs:273-274: final * colour
-                        out_r = thr_r * cr;
-                        out_g = thr_g * cg;
-                        out_b = thr_b * cb;
+                    } else {
+                        if (!kPlainEnd || !next) {  // common.rs:273-274: final * colour
+                            out_r = thr_r * cr;
+                            out_g = thr_g * cg;
+                            out_b = thr_b * cb;
+                        }
                         done = true;
+                    }
+                }
+                if constexpr (kPlainEnd) {
+                    // every path ends here: the store of below, inside the block
+                    if (done) {
+                        if constexpr (kPlainStore) {
+                            store_planes(sbase, pstride, slot, out_r, out_g, out_b);
+                        } else {
+                            sbase[slot] = out_r;
+                            sbase[pstride + slot] = out_g;
+                            sbase[2 * pstride + slot] = out_b;
+                        }
+                        active = false;
                     }
                 }
             }
             RT_STAMP(3);
-            if (done) {
+            if (!kPlainEnd && done) {
                 if (kSerial && p.mode == kRngSerialCheck) {
                     // the chain check: this sample's end state must be the next
                     // sample's start state (one variant: slot = launch sample)
@@ -796,10 +854,14 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
                 }
                 // planar (R, G, B planes): 12 B per sample, to the slab or the
                 // ring (SERIAL passes: plane 0 only)
-                sbase[slot] = out_r;
-                if (!kSerial) {
-                    sbase[pstride + slot] = out_g;
-                    sbase[2 * pstride + slot] = out_b;
+                if constexpr (kPlainStore) {
+                    store_planes(sbase, pstride, slot, out_r, out_g, out_b);
+                } else {
+                    sbase[slot] = out_r;
+                    if (!kSerial) {
+                        sbase[pstride + slot] = out_g;
+                        sbase[2 * pstride + slot] = out_b;
+                    }
                 }
                 active = false;
             }
@@ -824,6 +886,9 @@ __device__ __forceinline__ void trace_body(TraceParams p, const uint4 *corner) {
             const bool fin = !active && slot != ~0u;
             if (__ballot(fin) != 0) {
                 const uint32_t lk = slot >> p.ring_shift;
+                // (measured and dropped, DESIGN.md 5.4: the first finished lane's
+                // slot read with v_readlane and the other slots passed by on a
+                // scalar compare when no finished lane has another, C2 +2.4 %)
 #pragma unroll
                 for (uint32_t k = 0; k < kTraceRing; ++k) {
                     if (rfree & (1u << k)) continue;
