@@ -403,6 +403,106 @@ int rt_first_hit_view_device(const Rust_WorldHandle *handle, size_t width, size_
                              const RtFirstHitOptions *opts, int view, void *d_rgba,
                              void *hip_stream);
 
+/* ---- Edge-aware filter of a noisy frame, guided by first-hit records
+ * (DESIGN.md 5.9).
+ *
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over per-pixel
+ * mean colours, stopped at geometric edges by the records above: a viewer that
+ * has just moved the camera filters its 1 to 4 samples and shows the result,
+ * all on the device.  It is a preview filter, not a replacement for samples:
+ * on primitives a few pixels wide it blurs detail away.
+ *
+ * Inputs, for a width x height image, top row first: colours c (RGB f32),
+ * records g (RtFirstHit, as rt_first_hit_device writes them) and options.
+ * Every step below is one rounded f32 operation, unfused; divisions are
+ * correctly rounded; comparisons are false for NaN.
+ *
+ * Level l = 0 .. levels - 1 reads the previous level's colours (level 0 the
+ * input) and writes new ones; the records never change.  step = 1 << l,
+ * sl = sigma_l * 2^-l (exact), taps H = (1/16, 1/4, 3/8, 1/4, 1/16).
+ * Per centre pixel p: L_p = (r + g) + b of its input colour at this level,
+ * zs = sigma_z * t_p.  The taps q = p + ((i - 2) step, (j - 2) step), y growing
+ * downwards, are visited with j = 0..4 outer and i = 0..4 inner; sums are
+ * accumulated in that order.  Per tap:
+ *   1. q outside the image: skip.
+ *   2. hp = prim_p != 0, hq = prim_q != 0; hp != hq: skip.  With
+ *      RT_FILTER_SAME_PRIM, prim_p != prim_q: skip.
+ *   3. w = H[j] * H[i]
+ *   4. if hp: d = ((n_p.x*n_q.x) + (n_p.y*n_q.y)) + (n_p.z*n_q.z)
+ *             d = d > 0 ? d : 0;  normal_squarings times: d = d*d
+ *             v = pos_q - pos_p
+ *             e = fabs(((v.x*n_p.x) + (v.y*n_p.y)) + (v.z*n_p.z)) / zs
+ *             wz = 1 / (1 + e*e);  w = (w*d) * wz
+ *   5. el = fabs(L_q - L_p) / sl;  wl = 1 / (1 + el*el);  w = w * wl
+ *   6. if not w > 0: skip (NaN and zero weights)
+ *   7. num_k = num_k + w*c_q,k for k = r, g, b;  den = den + w
+ * Output channel k of p: den > 0 ? num_k / den : c_p,k.
+ * After the last level the f32 output is the colour and the RGBA8 output is
+ * sqrt(c_k) * 255.999 as u8 (Rust's saturating cast, as the frame resolve),
+ * alpha 255.  With levels = 0 the output is the input.
+ *
+ * On an accumulator the input colour of pixel p is sum_k * inv with
+ * inv = 1.0f / (float)n_p, n_p the samples held (rt_accum_samples) or, for an
+ * adaptive accumulator, count[p]: what the frame's resolve takes the square
+ * root of, so levels = 0 returns the last pass's frame byte for byte.  The
+ * records are the first-hit records at the accumulator's size with
+ * su = sv = 0.5, its accel and the camera its samples were traced with; they
+ * are kept until the camera moves or the scene is edited. */
+enum { RT_FILTER_SAME_PRIM = 1 };  /* flags: only taps on the centre's primitive count */
+
+typedef struct RtFilterOptions {
+  int32_t levels;             /* 0 .. 8; default 3 */
+  float sigma_l;              /* finite, > 0; default 0.5 */
+  float sigma_z;              /* finite, > 0; default 0.02 */
+  int32_t normal_squarings;   /* 0 .. 8; default 5 (the normals' dot to the power 32) */
+  uint32_t flags;             /* RT_FILTER_*; default 0 */
+} RtFilterOptions;
+
+typedef struct RtFilter RtFilter;   /* owns the per-size device scratch, one device */
+
+void rt_filter_default_options(RtFilterOptions *opts);
+/* A filter for width x height images on `device` (-1: the current device at
+ * its first run).  NULL + rt_last_error for a zero size or
+ * width * height >= 2^31.  Needs no GPU; running it does. */
+RtFilter *rt_filter_create(size_t width, size_t height, int device);
+void rt_filter_free(RtFilter *f);
+/* Every call below: opts NULL = the defaults; returns 0 or a negative error
+ * with rt_last_error naming the call and the argument.  Checked before a
+ * device is looked for: a null filter or accumulator, a null input, both
+ * outputs null (either one may be), levels, sigma_l, sigma_z or
+ * normal_squarings out of range, unknown flag bits.  rgb buffers are
+ * width * height * 3 f32, interleaved, top row first (rt_accum_read's layout).
+ *
+ * Any image, any records: DEVICE buffers, only enqueued on hip_stream.  NULL =
+ * the library's stream for this filter: a filter belongs to no world, so it
+ * is a non-blocking stream of the filter's own, which is NOT ordered against
+ * the null stream -- a caller whose inputs are produced on another stream
+ * (the null stream included) passes that stream, or synchronises first, and
+ * waits for the device before reading the outputs.  d_records must be
+ * 16-byte aligned (the records are read as 16-byte halves; hipMalloc'd
+ * memory is); d_rgb and the outputs need only their elements' alignment.
+ * d_out_rgb == d_rgb is allowed (the input is repacked before the first
+ * level). */
+int rt_filter_run_device(RtFilter *f, const RtFilterOptions *opts, const float *d_rgb,
+                         const void *d_records, float *d_out_rgb, void *d_out_rgba,
+                         void *hip_stream);
+/* The same from and to host memory, synchronous. */
+int rt_filter_run(RtFilter *f, const RtFilterOptions *opts, const float *rgb,
+                  const RtFirstHit *records, float *out_rgb, Rust_ColorU8 *out_pixels);
+/* The accumulator's held samples, filtered: to host memory (synchronous), or
+ * to device memory on hip_stream (NULL = the library's stream; only
+ * enqueued).  Takes the handle's lock and is ordered after the accumulator's
+ * last pass like its other calls.  Fails with "no samples held" when the
+ * accumulator holds none -- also when its next add would reset it because the
+ * camera moved or the scene was edited -- and when its world was freed.  The
+ * filter's size limit is lower than the accumulator's: an accumulator of
+ * 2^31 pixels or more (rt_accum_create takes up to 2^32 - 1) cannot be
+ * filtered, and the call says so. */
+int rt_filter_accum(RtAccum *acc, const RtFilterOptions *opts, float *out_rgb,
+                    Rust_ColorU8 *pixels);
+int rt_filter_accum_device(RtAccum *acc, const RtFilterOptions *opts, float *d_out_rgb,
+                           void *d_rgba, void *hip_stream);
+
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).
  * That launch must have been rendered with RT_FLAG_KEEP_SAMPLES.  Output

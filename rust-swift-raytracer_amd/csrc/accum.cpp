@@ -28,7 +28,10 @@ WorldState *accum_world(AccumState &a) {
 // The held samples count only for the camera and scene they were traced with
 // (the 12 camera floats compared as bits: a camera moved away and back matches)
 void accum_check_state(AccumState &a, WorldState &w, const float cam[12]) {
-    if (a.held != 0 && (std::memcmp(a.cam, cam, sizeof(a.cam)) != 0 || a.edit_version != w.edit_version)) a.held = 0;
+    if (a.held != 0 && (std::memcmp(a.cam, cam, sizeof(a.cam)) != 0 || a.edit_version != w.edit_version)) {
+        a.held = 0;
+        a.rec_valid = false;  // (the filter's records go with the sums)
+    }
 }
 
 void accum_release(AccumState *a) {
@@ -255,14 +258,15 @@ int accum_reset(AccumState &a) {
     if (!wp) return -1;
     std::lock_guard<std::recursive_mutex> lock(wp->mu);
     a.held = 0;
+    a.rec_valid = false;
     return 0;
 }
 
 // ------------------------------------------------------------ adaptive accumulation
 // (rt_adapt_*: DESIGN.md 5.7)
-namespace {
 // the accumulator's world, locked, after the reset rule; nullptr with the error set
-WorldState *adapt_begin(AccumState &a, const CameraModel &cam, std::unique_lock<std::recursive_mutex> &lock) {
+// (runtime_internal.h: filter.cpp begins its accumulator calls the same way)
+WorldState *accum_begin(AccumState &a, const CameraModel &cam, std::unique_lock<std::recursive_mutex> &lock) {
     WorldState *wp = accum_world(a);
     if (!wp) return nullptr;
     lock = std::unique_lock<std::recursive_mutex>(wp->mu);
@@ -271,12 +275,11 @@ WorldState *adapt_begin(AccumState &a, const CameraModel &cam, std::unique_lock<
     accum_check_state(a, *wp, cf);
     return wp;
 }
-}  // namespace
 
 int adapt_enable(AccumState &a, const CameraModel &cam, float tolerance, float bias, uint32_t min_samples) {
     // (the options were checked by rt_adapt_enable, before the accumulator)
     std::unique_lock<std::recursive_mutex> lock;
-    WorldState *wp = adapt_begin(a, cam, lock);
+    WorldState *wp = accum_begin(a, cam, lock);
     if (!wp) return -1;
     if (a.held != 0) {
         set_error("rt_adapt_enable: the accumulator holds " + std::to_string(a.held) + " samples (reset it first)");
@@ -305,7 +308,7 @@ int adapt_enable(AccumState &a, const CameraModel &cam, float tolerance, float b
 
 int adapt_disable(AccumState &a, const CameraModel &cam) {
     std::unique_lock<std::recursive_mutex> lock;
-    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!accum_begin(a, cam, lock)) return -1;
     if (a.held != 0) {
         set_error("rt_adapt_disable: the accumulator holds " + std::to_string(a.held) + " samples (reset it first)");
         return -1;
@@ -316,7 +319,7 @@ int adapt_disable(AccumState &a, const CameraModel &cam) {
 
 long adapt_active(AccumState &a, const CameraModel &cam) {
     std::unique_lock<std::recursive_mutex> lock;
-    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!accum_begin(a, cam, lock)) return -1;
     return a.adaptive && a.held != 0 ? (long)a.nactive : (long)(a.width * a.height);
 }
 
@@ -325,7 +328,7 @@ namespace {
 int adapt_read_plane(AccumState &a, const CameraModel &cam, bool counts, void *out, const char *who) {
     if (!out) { set_error(std::string(who) + ": null output"); return -1; }
     std::unique_lock<std::recursive_mutex> lock;
-    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!accum_begin(a, cam, lock)) return -1;
     if (!a.adaptive) { set_error(std::string(who) + ": the accumulator is not adaptive"); return -1; }
     const size_t npix = a.width * a.height;
     if (a.held == 0) {
@@ -350,7 +353,7 @@ int adapt_read_sumsq(AccumState &a, const CameraModel &cam, float *sumsq) {
 
 long adapt_read_active(AccumState &a, const CameraModel &cam, uint32_t *list, size_t cap) {
     std::unique_lock<std::recursive_mutex> lock;
-    if (!adapt_begin(a, cam, lock)) return -1;
+    if (!accum_begin(a, cam, lock)) return -1;
     if (!a.adaptive) { set_error("rt_adapt_read_active: the accumulator is not adaptive"); return -1; }
     const size_t npix = a.width * a.height;
     if (a.held == 0) {  // (every pixel, ascending: what the next pass starts from)

@@ -27,6 +27,9 @@ struct RtAccum {
     const Rust_WorldHandle *handle;
     rtamd::AccumState *state;
 };
+struct RtFilter {
+    rtamd::FilterState *state;
+};
 
 namespace {
 thread_local int g_parse_status = rtamd::kParseOk;
@@ -562,6 +565,52 @@ int rt_first_hit_view_device(const Rust_WorldHandle *h, size_t width, size_t hei
                              int view, void *d_rgba, void *hip_stream) {
     return first_hit_call(h, width, height, opts, true, view, d_rgba, hip_stream, nullptr,
                           "rt_first_hit_view_device");
+}
+
+// ---- edge-aware filter
+void rt_filter_default_options(RtFilterOptions *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->levels = 3;
+    o->sigma_l = 0.5f;
+    o->sigma_z = 0.02f;
+    o->normal_squarings = 5;
+}
+
+RtFilter *rt_filter_create(size_t width, size_t height, int device) {
+    rtamd::FilterState *st = rtamd::filter_create(width, height, device);
+    return st ? new RtFilter{st} : nullptr;
+}
+
+void rt_filter_free(RtFilter *f) {
+    if (!f) return;
+    delete f->state;
+    delete f;
+}
+
+int rt_filter_run_device(RtFilter *f, const RtFilterOptions *opts, const float *d_rgb, const void *d_records,
+                         float *d_out_rgb, void *d_out_rgba, void *hip_stream) {
+    return rtamd::filter_run(f ? f->state : nullptr, opts, d_rgb, d_records, d_out_rgb, d_out_rgba, true,
+                             static_cast<hipStream_t>(hip_stream), "rt_filter_run_device");
+}
+
+int rt_filter_run(RtFilter *f, const RtFilterOptions *opts, const float *rgb, const RtFirstHit *records,
+                  float *out_rgb, Rust_ColorU8 *out_pixels) {
+    return rtamd::filter_run(f ? f->state : nullptr, opts, rgb, records, out_rgb, out_pixels, false, nullptr,
+                             "rt_filter_run");
+}
+
+int rt_filter_accum(RtAccum *acc, const RtFilterOptions *opts, float *out_rgb, Rust_ColorU8 *pixels) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_filter_accum");
+    if (!cam) return -1;
+    return rtamd::filter_accum(acc->state, cam, opts, out_rgb, pixels, false, nullptr, "rt_filter_accum");
+}
+
+int rt_filter_accum_device(RtAccum *acc, const RtFilterOptions *opts, float *d_out_rgb, void *d_rgba,
+                           void *hip_stream) {
+    const rtamd::CameraModel *cam = accum_camera(acc, "rt_filter_accum_device");
+    if (!cam) return -1;
+    return rtamd::filter_accum(acc->state, cam, opts, d_out_rgb, d_rgba, true, static_cast<hipStream_t>(hip_stream),
+                               "rt_filter_accum_device");
 }
 
 int rt_device_count(void) {

@@ -355,6 +355,38 @@ struct FirstHitTail {
     uint32_t view;
 };
 hipError_t launch_first_hit(const TraceParams &p, const FirstHitTail &tail, hipStream_t stream);
+// The edge-aware filter (filter.hip; DESIGN.md 5.9, include/raytracer_amd.h
+// rt_filter_*).  pack: one lane per pixel writes col[i] = {r, g, b, (r + g) + b}
+// and, from the 32-byte first-hit records, g0[i] = {normal, prim bits} and
+// g1[i] = {position, sigma_z * t}.  The colour is rgb[3 i + k] (interleaved),
+// or, with rgb null, sums[k * plane + i] * inv with inv = 1.0f / (float)n and
+// n = count[i] where count is given, else held.
+struct FilterPack {
+    const float *rgb;
+    const float *sums;
+    size_t plane;
+    const uint32_t *count;
+    uint32_t held;
+    const float4 *records;
+    float sigma_z;
+    float4 *col, *g0, *g1;
+    uint32_t npix;
+};
+hipError_t launch_filter_pack(const FilterPack &a, hipStream_t stream);
+// level: one a-trous level of step `step` over width x height, cin -> cout; the
+// last level (cout null) writes out_rgb (3 f32 per pixel) and / or out_rgba
+// (RGBA8 words) instead.  step 0: no level, the outputs from cin (levels = 0).
+struct FilterLevel {
+    const float4 *cin, *g0, *g1;
+    float4 *cout;
+    float *out_rgb;
+    uint32_t *out_rgba;
+    uint32_t width, height, step;
+    float sl;                  // sigma_l * 2^-level
+    uint32_t squarings;
+    uint32_t same_prim;
+};
+hipError_t launch_filter_level(const FilterLevel &a, hipStream_t stream);
 // The adaptive accumulator's list kernels (adapt.hip).  iota: list[i] = i.
 // select: one thread per entry i < n of list: count[list[i]] = N and, with
 // decide, keep[i] = 0 iff the pixel converged by the rule of DESIGN.md 5.7

@@ -20,6 +20,7 @@
 struct RtRenderOptions;
 struct RtRenderStats;
 struct RtFirstHitOptions;
+struct RtFilterOptions;
 
 namespace rtamd {
 
@@ -233,6 +234,24 @@ struct WorldState {
     ~WorldState();
 };
 
+// An edge-aware filter's scratch for one image size on one device (DESIGN.md
+// 5.9, rt_filter_*): the ping-pong colours and the packed guides a level
+// gathers, and staging for the host entries.  Everything is allocated by the
+// first run (a filter can be created without a GPU; running it fails there).
+struct FilterState {
+    size_t width = 0, height = 0;
+    int device = -1;              // < 0: the current device at the first run
+    DevBuf<float4> col[2];        // {r, g, b, L}: a level reads one, writes the other
+    DevBuf<float4> g0, g1;        // {normal, prim bits}, {position, sigma_z * t}
+    DevBuf<float> in_rgb, out_rgb;        // host entries: staging
+    DevBuf<uint32_t> in_rec, out_rgba;
+    hipStream_t stream = nullptr; // its own (rt_filter_run; rt_filter_run_device with a null stream)
+    hipEvent_t done = nullptr;    // end of the last run enqueued ...
+    hipStream_t done_stream = nullptr;  // ... and its stream: a run on another waits for it
+    std::mutex mu;                // one run at a time per filter
+    ~FilterState();
+};
+
 // A progressive accumulation: per-pixel f32 sums of sample
 // colours for one world, frame size and camera, on one device, filled in
 // passes.  Owns the sum planes and, in REPLAY mode, the device copy of its
@@ -268,6 +287,15 @@ struct AccumState {
     DevBuf<uint32_t> totals;      // the compaction's block totals
     DevBuf<uint32_t> d_len;       // the new list length on the device ...
     PinnedBuf<uint32_t> h_len;    // ... and in pinned host memory
+    // The filter of the held samples (rt_filter_accum): created
+    // by the first call; the first-hit records of the frame (su = sv = 0.5,
+    // this accel) for rec_cam and rec_edit, rebuilt when those differ from cam
+    // and edit_version and dropped with the sums (rec_valid).
+    std::unique_ptr<FilterState> filter;
+    DevBuf<uint32_t> records;     // width * height RtFirstHit
+    float rec_cam[12] = {};
+    uint64_t rec_edit = 0;
+    bool rec_valid = false;
 };
 
 // One pass of an accumulation, for render_frame: n0 samples held, the frame's
@@ -355,6 +383,20 @@ struct FirstHitPick { size_t col, row; };
 int first_hit(WorldState &w, const CameraModel &cam, size_t width, size_t height, const RtFirstHitOptions *opts,
               bool views, int view, void *d_out, hipStream_t stream, void *host_out, const char *who,
               const FirstHitPick *pick = nullptr);
+// The edge-aware filter (rt_filter_*, include/raytracer_amd.h).
+// Every call checks its arguments with a message (who: the entry point) before
+// it looks for a device.  create: the size only (nullptr with the error set).
+// run: width x height interleaved colours and RtFirstHit records in, the
+// filtered colours (f32) and / or their RGBA8 out; on_device: all four are
+// device memory and the run is only enqueued on stream (null: the filter's
+// own), else host memory and the call waits.  accum: the same on the
+// accumulator's held samples (means of the sums, the accumulator's cached
+// first-hit records), stream null: the device's library stream.
+FilterState *filter_create(size_t width, size_t height, int device);
+int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, const void *records, float *out_rgb,
+               void *out_rgba, bool on_device, hipStream_t stream, const char *who);
+int filter_accum(AccumState *a, const CameraModel *cam, const RtFilterOptions *opts, float *out_rgb, void *out_rgba,
+                 bool on_device, hipStream_t stream, const char *who);
 // Waits for device d's pending counted frame and fills stats from it.
 int collect_frame_stats(DeviceState *d, RtRenderStats *stats);
 

@@ -81,6 +81,10 @@ int serial_check_args(size_t width, size_t height, const RtRenderOptions &o);
 int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size_t height,
                        const RtRenderOptions &o, DeviceState *d, hipStream_t s, RtRenderStats *stats);
 
+// accum.cpp: the accumulator's world, locked, after the reset rule (a moved
+// camera or an edited scene drops the held samples); nullptr with the error set
+WorldState *accum_begin(AccumState &a, const CameraModel &cam, std::unique_lock<std::recursive_mutex> &lock);
+
 // multi.cpp: devices [first, first + n) (first < 0: from the current device), checked
 int device_list(int first, int n, std::vector<int> &devs);
 

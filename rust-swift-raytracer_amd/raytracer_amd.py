@@ -24,6 +24,7 @@ FLAG_KEEP_SAMPLES = 1
 FLAG_SERIAL_CHECK = 2
 DEFAULT_SEED = 2547549
 VIEW_NORMAL, VIEW_DEPTH, VIEW_ALBEDO, VIEW_PRIM = 0, 1, 2, 3
+FILTER_SAME_PRIM = 1
 
 # Every symbol declared in include/raytracer.h and include/raytracer_amd.h.
 EXPORTS = (
@@ -42,6 +43,8 @@ EXPORTS = (
     "rt_camera_translate", "rt_camera_free", "rt_primary_tri_lists", "rt_camera_record_builds",
     "rt_first_hit_default_options", "rt_first_hit", "rt_first_hit_device", "rt_first_hit_pick",
     "rt_first_hit_view", "rt_first_hit_view_device",
+    "rt_filter_default_options", "rt_filter_create", "rt_filter_free", "rt_filter_run_device",
+    "rt_filter_run", "rt_filter_accum", "rt_filter_accum_device",
 )
 
 
@@ -93,6 +96,12 @@ FIRST_HIT_DTYPE = np.dtype([("prim", "<u4"), ("t", "<f4"), ("normal", "<f4", (3,
 class FirstHitOptions(C.Structure):
     _fields_ = [("su", C.c_float), ("sv", C.c_float), ("x0", C.c_uint32), ("y0", C.c_uint32),
                 ("w", C.c_uint32), ("h", C.c_uint32), ("device", C.c_int32), ("accel", C.c_int32)]
+
+
+class FilterOptions(C.Structure):
+    """raytracer_amd.h RtFilterOptions (defaults: 3, 0.5, 0.02, 5, 0)."""
+    _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("normal_squarings", C.c_int32), ("flags", C.c_uint32)]
 
 
 class RenderStats(C.Structure):
@@ -256,6 +265,23 @@ def lib(path=None):
             L.rt_first_hit_view.argtypes = [H, C.c_size_t, C.c_size_t, FO, C.c_int, C.POINTER(ColorU8)]
             L.rt_first_hit_view_device.restype = C.c_int
             L.rt_first_hit_view_device.argtypes = [H, C.c_size_t, C.c_size_t, FO, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_filter_create"):  # (likewise)
+            LO = C.POINTER(FilterOptions)
+            L.rt_filter_default_options.restype = None
+            L.rt_filter_default_options.argtypes = [LO]
+            L.rt_filter_create.restype = C.c_void_p
+            L.rt_filter_create.argtypes = [C.c_size_t, C.c_size_t, C.c_int]
+            L.rt_filter_free.restype = None
+            L.rt_filter_free.argtypes = [C.c_void_p]
+            L.rt_filter_run_device.restype = C.c_int
+            L.rt_filter_run_device.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+            L.rt_filter_run.restype = C.c_int
+            L.rt_filter_run.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rt_filter_accum.restype = C.c_int
+            L.rt_filter_accum.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p]
+            L.rt_filter_accum_device.restype = C.c_int
+            L.rt_filter_accum_device.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[path] = L
     return _libs[path]
 
@@ -678,12 +704,93 @@ class Accumulator:
                     "rt_adapt_read_sumsq")
         return out
 
+    # ---- the held samples, filtered (rt_filter_accum*)
+    def filtered(self, **opts):
+        """rt_filter_accum -> (rgb float32[height, width, 3], rgba uint8[height, width, 4]);
+        options as filter_options (levels, sigma_l, sigma_z, normal_squarings, flags)."""
+        o = filter_options(self._L, **opts)
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        px = np.zeros((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rt_filter_accum(self._a, C.byref(o), out.ctypes.data, px.ctypes.data), "rt_filter_accum")
+        return out, px
+
+    def filtered_device(self, out_rgb_ptr: int = 0, out_rgba_ptr: int = 0, stream_ptr: int = 0, **opts):
+        """rt_filter_accum_device: into device memory, only enqueued on the stream."""
+        o = filter_options(self._L, **opts)
+        self._check(self._L.rt_filter_accum_device(self._a, C.byref(o), C.c_void_p(out_rgb_ptr or None),
+                                                   C.c_void_p(out_rgba_ptr or None),
+                                                   C.c_void_p(stream_ptr or None)), "rt_filter_accum_device")
+
     def active_list(self):
         """The active list: uint32 frame indices (row * width + col, top row first), ascending."""
         out = np.zeros(self.width * self.height, np.uint32)
         n = self._check(self._L.rt_adapt_read_active(self._a, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size),
                         "rt_adapt_read_active")
         return out[:n].copy()
+
+
+def filter_options(L=None, **opts):
+    """rt_filter_default_options with the fields given overridden (levels, sigma_l,
+    sigma_z, normal_squarings, flags; same_prim=True sets FILTER_SAME_PRIM)."""
+    o = FilterOptions()
+    (L or lib()).rt_filter_default_options(C.byref(o))
+    if opts.pop("same_prim", False):
+        o.flags |= FILTER_SAME_PRIM
+    for k, v in opts.items():
+        if k not in ("levels", "sigma_l", "sigma_z", "normal_squarings", "flags"):
+            raise TypeError(f"unknown filter option {k!r}")
+        setattr(o, k, (o.flags | v) if k == "flags" else v)
+    return o
+
+
+class Filter:
+    """rt_filter_*: the edge-aware filter for width x height images."""
+
+    def __init__(self, width, height, device=-1, lib_path=None):
+        self._L = lib(lib_path)
+        self.width, self.height = width, height
+        self._f = self._L.rt_filter_create(width, height, device)
+        if not self._f:
+            raise RenderError(f"rt_filter_create failed: {self._L.rt_last_error().decode()}")
+
+    def close(self):
+        if getattr(self, "_f", None):
+            self._L.rt_filter_free(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, rgb, records, want_rgb=True, want_rgba=True, **opts):
+        """rt_filter_run: rgb float32[height, width, 3] and records FIRST_HIT_DTYPE[height,
+        width] -> (rgb float32[height, width, 3], rgba uint8[height, width, 4]); an output
+        not wanted is None."""
+        o = filter_options(self._L, **opts)
+        c = np.ascontiguousarray(rgb, dtype=np.float32)
+        g = np.ascontiguousarray(records, dtype=FIRST_HIT_DTYPE)
+        if c.size != 3 * self.width * self.height or g.size != self.width * self.height:
+            raise ValueError("rgb is height x width x 3 floats, records height x width")
+        out = np.zeros((self.height, self.width, 3), np.float32) if want_rgb else None
+        px = np.zeros((self.height, self.width, 4), np.uint8) if want_rgba else None
+        rc = self._L.rt_filter_run(self._f, C.byref(o), c.ctypes.data, g.ctypes.data,
+                                   out.ctypes.data if want_rgb else None, px.ctypes.data if want_rgba else None)
+        if rc != 0:
+            raise RenderError(f"rt_filter_run failed ({rc}): {self._L.rt_last_error().decode()}")
+        return out, px
+
+    def run_device(self, rgb_ptr: int, records_ptr: int, out_rgb_ptr: int = 0, out_rgba_ptr: int = 0,
+                   stream_ptr: int = 0, **opts):
+        """rt_filter_run_device: device buffers, only enqueued on the stream (0: the
+        filter's own); an output pointer of 0 is not written."""
+        o = filter_options(self._L, **opts)
+        rc = self._L.rt_filter_run_device(self._f, C.byref(o), C.c_void_p(rgb_ptr or None),
+                                          C.c_void_p(records_ptr or None), C.c_void_p(out_rgb_ptr or None),
+                                          C.c_void_p(out_rgba_ptr or None), C.c_void_p(stream_ptr or None))
+        if rc != 0:
+            raise RenderError(f"rt_filter_run_device failed ({rc}): {self._L.rt_last_error().decode()}")
 
 
 def write_ppm(rgba: np.ndarray, path: str):
