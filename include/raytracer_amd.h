@@ -527,6 +527,25 @@ int rt_leaf_defer(const Rust_WorldHandle *handle, int device);
  * bit-identical frames.  Negative: an error. */
 int rt_trace_plain(const Rust_WorldHandle *handle, int device);
 
+/* Diagnostics: which trace-kernel instances were launched on `device` (-1 =
+ * current) since the set was last cleared -- by frames, accumulation and
+ * adaptive passes and the passes of a SERIAL frame.  The library compiles one
+ * instance per combination of sphere search (0 brute force, 1 tree in global
+ * memory, 2 LDS box records, 3 LDS corner records), sliced walk (0 / 1),
+ * triangle search (0 none, 1 brute force, 2 binary tree, 3 its 4-wide image)
+ * and kind (0 lean, 1 counted, 2 SERIAL pass, 3 accumulation pass, 4 adaptive
+ * pass), at key ((search * 2 + step) * 4 + mesh) * 5 + kind, then the lean
+ * corner kernel's deferred-leaf instance (key 160) and its plain twin (161).
+ * Copies min(n, keys) bytes to `out` (may be NULL), 1 for each key launched,
+ * clears the set when `clear` is nonzero, and returns the number of keys.
+ * Negative: an error. */
+int rt_trace_launched(const Rust_WorldHandle *handle, int device, unsigned char *out, size_t n,
+                      int clear);
+/* ... and which keys the library holds an instance for at all (some
+ * combinations are served by another: DESIGN.md 5.1), 1 per such key.  Needs
+ * no device.  Returns the number of keys. */
+int rt_trace_instances(unsigned char *out, size_t n);
+
 /* Frees a handle from load_world (the reference never frees, lib.rs:42-45). */
 void rt_free_world(Rust_WorldHandle *handle);
 

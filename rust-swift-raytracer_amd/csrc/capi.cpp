@@ -219,6 +219,16 @@ int rt_leaf_defer(const Rust_WorldHandle *h, int device) {
     return rtamd::leaf_defer(h->world->state, device);
 }
 
+int rt_trace_launched(const Rust_WorldHandle *h, int device, unsigned char *out, size_t n, int clear) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_trace_launched: null argument");
+        return -1;
+    }
+    return rtamd::trace_launched(h->world->state, device, out, n, clear != 0);
+}
+
+int rt_trace_instances(unsigned char *out, size_t n) { return rtamd::trace_instances(out, n); }
+
 long rt_read_samples(const Rust_WorldHandle *h, int device, float *out, size_t n) {
     if (!h || !h->world || !out) {
         rtamd::set_error("rt_read_samples: null argument");

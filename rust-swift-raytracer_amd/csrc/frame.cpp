@@ -455,6 +455,14 @@ int choose_kernel_instance(DeviceState *d, const SerialPass *sp, const AccumPass
     return 0;
 }
 
+// launch_trace, with the instance it ran noted in the device's set (rt_trace_launched)
+hipError_t launch_recorded(DeviceState *d, TraceVariant v, const TraceParams &p, const TraceTail &tail,
+                           uint32_t blocks, hipStream_t s) {
+    const hipError_t e = launch_trace(v, p, tail, blocks, s);
+    if (e == hipSuccess) d->trace_launched[trace_key(v)] = 1;
+    return e;
+}
+
 // One SERIAL pass instead of a frame (serial_states.cpp's inner launches).
 // Its chunk and partition formula is its own, tuned apart from plan_launch's.
 int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRenderOptions &o,
@@ -515,7 +523,7 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
     if (sp->mode == kRngSerialPixel) {
         // (job counters zeroed by serial_window_kernel, kPixtabParts of them)
         p.nparts = (uint32_t)std::min<uint64_t>(parts, kPixtabParts);
-        HIP_TRY(launch_trace(resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
+        HIP_TRY(launch_recorded(d, resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
     } else if (sp->mode == kRngSerialCoalesce) {
         // one workgroup per block of sp->R samples; the tree in LDS when it
         // fits beside the search's own arrays (64 KB per workgroup)
@@ -524,7 +532,7 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
                                        sp->dbg, s));
     } else {
         HIP_TRY(hipMemsetAsync(d->counter.get(), 0, parts * 128, s));
-        HIP_TRY(launch_trace(resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
+        HIP_TRY(launch_recorded(d, resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
     }
     HIP_TRY(hipEventRecord(d->done, s));
     d->done_stream = s;
@@ -660,7 +668,7 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             // the launch's instance, resolved once (chunk, ring and gj32 are set per launch)
             const TraceVariant v = resolve_trace_variant(p, f.want);
             if (adapt) tail.list = ap->list + r0;
-            HIP_TRY(launch_trace(v, p, tail, (uint32_t)blocks, s));
+            HIP_TRY(launch_recorded(d, v, p, tail, (uint32_t)blocks, s));
             done.variant = v;
             d->last_leaf_defer = trace_leaf_defer(v);
             d->last_plain = v.leaf == TraceLeaf::Plain;
@@ -895,6 +903,22 @@ int trace_plain(WorldState &w, int device) {
     int rc = device_for(w, device, d);
     if (rc) return rc;
     return d->last_plain ? 1 : 0;
+}
+
+int trace_launched(WorldState &w, int device, uint8_t *out, size_t n, bool clear) {
+    std::lock_guard<std::recursive_mutex> lock(w.mu);  // (device_for may add a device)
+    DeviceState *d = nullptr;
+    int rc = device_for(w, device, d);
+    if (rc) return rc;
+    if (out) std::memcpy(out, d->trace_launched, std::min<size_t>(n, kTraceKeys));
+    if (clear) std::memset(d->trace_launched, 0, sizeof(d->trace_launched));
+    return kTraceKeys;
+}
+
+int trace_instances(uint8_t *out, size_t n) {
+    for (int key = 0; key < kTraceKeys && (size_t)key < n && out; ++key)
+        out[key] = trace_instance_exists(key) ? 1 : 0;
+    return kTraceKeys;
 }
 
 int primary_tri_lists(WorldState &w, int device) {

@@ -579,6 +579,8 @@ constexpr uint32_t kLdsTreeMaxNodes = 1023;
 // threads per workgroup of an instance (LDS-tree kernels: per family and kind;
 // the others 256)
 uint32_t trace_block_threads(TraceVariant v);
+// the table holds an instance at this key (trace_key; no device needed)
+bool trace_instance_exists(int key);
 // dynamic LDS of one trace workgroup: the sphere tree (LDS searches) and, for
 // the wide triangle walk, every lane's stack (u16 entries)
 size_t trace_dyn_lds(const TraceParams &p, TraceVariant v);

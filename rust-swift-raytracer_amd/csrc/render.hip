@@ -274,6 +274,10 @@ static const TraceInstance &trace_instance(TraceVariant v) {
 
 uint32_t trace_block_threads(TraceVariant v) { return trace_instance(v).threads; }
 
+bool trace_instance_exists(int key) {
+    return key >= 0 && key < kTraceKeys && trace_instance(trace_variant_at(key)).fn != nullptr;
+}
+
 size_t trace_lds_bytes(const TraceParams &p, bool corner) {
     // (shading records in global memory instead, which would allow 8 waves per
     // SIMD: A/B +1.7 % at 6 waves, +8 % at 8 waves per SIMD)

@@ -193,6 +193,9 @@ struct DeviceState {
     bool last_fused = false;                                    // it resolved in-kernel (no slab)
     int last_leaf_defer = 0;                                    // its walk's pending leaves per lane (rt_leaf_defer)
     bool last_plain = false;                                    // it ran the plain instance (rt_trace_plain)
+    // the instances launched on this device since the last clear, one byte per
+    // render.h trace_key (rt_trace_launched): frames, passes and SERIAL passes
+    uint8_t trace_launched[kTraceKeys] = {};
     ~DeviceState();
 };
 
@@ -438,6 +441,13 @@ void prepare_camera(WorldState &w, const CameraModel &cam, bool tree = false);
 long read_samples(WorldState &w, int device, float *out, size_t n);
 int leaf_defer(WorldState &w, int device);
 int trace_plain(WorldState &w, int device);
+// the device's set of launched instances into out (n bytes at most, one per
+// render.h trace_key; out may be null), cleared afterwards when asked -> kTraceKeys
+// (rt_trace_launched)
+int trace_launched(WorldState &w, int device, uint8_t *out, size_t n, bool clear);
+// one byte per trace_key, 1 where the library has an instance; no device needed
+// (rt_trace_instances)
+int trace_instances(uint8_t *out, size_t n);
 // where the last frame launch's primary triangle lists were built (rt_primary_tri_lists)
 int primary_tri_lists(WorldState &w, int device);
 

@@ -38,7 +38,7 @@ EXPORTS = (
     "rt_accum_samples", "rt_accum_read", "rt_accum_reset", "rt_accum_free",
     "rt_adapt_default_options", "rt_adapt_enable", "rt_adapt_disable", "rt_adapt_active",
     "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active", "rt_leaf_defer",
-    "rt_trace_plain",
+    "rt_trace_plain", "rt_trace_launched", "rt_trace_instances",
     "rt_camera_new_with_vertical_fov", "rt_camera_new_look_at", "rt_camera_from_floats",
     "rt_camera_translate", "rt_camera_free", "rt_primary_tri_lists", "rt_camera_record_builds",
     "rt_first_hit_default_options", "rt_first_hit", "rt_first_hit_device", "rt_first_hit_pick",
@@ -205,6 +205,11 @@ def lib(path=None):
         if hasattr(L, "rt_trace_plain"):  # (likewise)
             L.rt_trace_plain.restype = C.c_int
             L.rt_trace_plain.argtypes = [H, C.c_int]
+        if hasattr(L, "rt_trace_launched"):  # (likewise)
+            L.rt_trace_launched.restype = C.c_int
+            L.rt_trace_launched.argtypes = [H, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int]
+            L.rt_trace_instances.restype = C.c_int
+            L.rt_trace_instances.argtypes = [C.POINTER(C.c_uint8), C.c_size_t]
         if hasattr(L, "rt_camera_new_look_at"):  # (likewise)
             L.rt_camera_new_with_vertical_fov.restype = C.c_void_p
             L.rt_camera_new_with_vertical_fov.argtypes = [fp, C.c_float, C.c_float]
@@ -284,6 +289,15 @@ def lib(path=None):
             L.rt_filter_accum_device.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[path] = L
     return _libs[path]
+
+
+def trace_instances(L=None) -> np.ndarray:
+    """rt_trace_instances: uint8 per trace-kernel key, 1 where the library holds an
+    instance (raytracer_amd.h rt_trace_launched spells the key).  Needs no device."""
+    L = L or lib()
+    out = np.zeros(L.rt_trace_instances(None, 0), np.uint8)
+    L.rt_trace_instances(out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size)
+    return out
 
 
 def last_error() -> str:
@@ -519,6 +533,16 @@ class World:
         if n < 0:
             raise RenderError(f"rt_trace_plain failed ({n}): {self._L.rt_last_error().decode()}")
         return n
+
+    def trace_launched(self, clear=False, device=-1):
+        """rt_trace_launched: uint8 per trace-kernel key, 1 for each instance launched
+        on the device since the set was last cleared (clear=True: cleared after the read)."""
+        out = np.zeros(self._L.rt_trace_instances(None, 0), np.uint8)
+        n = self._L.rt_trace_launched(self._h, device, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
+                                      1 if clear else 0)
+        if n < 0:
+            raise RenderError(f"rt_trace_launched failed ({n}): {self._L.rt_last_error().decode()}")
+        return out
 
     def render_device(self, width, height, out_ptr: int, stream_ptr: int = 0, spp=16, depth=8,
                       mode=RNG_COUNTER, seed=DEFAULT_SEED, row_block=8, rank=0, nranks=1,
