@@ -209,7 +209,9 @@ int rt_render_device(const Rust_WorldHandle *handle, size_t width, size_t height
  *
  * Ownership: free the accumulator before its world.  After rt_free_world
  * every call on the accumulator but rt_accum_free fails with an error (it
- * does not touch the freed handle).  Calls on one handle's accumulators and
+ * does not touch the freed handle); rt_free_world waits for the calls on the
+ * world's accumulators that other threads are in, so such a call either
+ * completes or fails with that error.  Calls on one handle's accumulators and
  * frames are serialised by the handle's lock. */
 typedef struct RtAccum RtAccum;
 

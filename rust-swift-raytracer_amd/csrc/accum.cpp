@@ -2,6 +2,7 @@
 // rt_adapt_*: DESIGN.md 5.6, 5.7): an accumulator's lifetime, its passes
 // through render_frame and its reads.
 #include <algorithm>
+#include <condition_variable>
 
 #include "runtime_internal.h"
 
@@ -10,9 +11,10 @@ namespace rtamd {
 // ------------------------------------------------------------ accumulation
 // (rt_accum_*: DESIGN.md 5.6)
 namespace {
-// guards AccumState::world and WorldState::accums (a world freed before its
-// accumulators detaches them)
+// guards AccumState::world, WorldState::accums and WorldState::accum_calls (a
+// world freed before its accumulators detaches them); g_accum_cv: a call left
 std::mutex g_accum_mu;
+std::condition_variable g_accum_cv;
 
 void camera_floats(const CameraModel &cam, float out[12]) {
     const Vec3 cv[4] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical};
@@ -47,6 +49,28 @@ void accum_release(AccumState *a) {
 WorldState::~WorldState() {
     std::lock_guard<std::mutex> g(g_accum_mu);
     for (AccumState *a : accums) a->world = nullptr;
+}
+
+WorldState *accum_enter(AccumState &a) {
+    std::lock_guard<std::mutex> g(g_accum_mu);
+    if (a.world) ++a.world->accum_calls;
+    return a.world;
+}
+
+void accum_leave(WorldState *w) {
+    {
+        std::lock_guard<std::mutex> g(g_accum_mu);
+        --w->accum_calls;
+    }
+    g_accum_cv.notify_all();
+}
+
+void world_retire(WorldState &w) {
+    std::unique_lock<std::mutex> g(g_accum_mu);
+    for (AccumState *a : w.accums) a->world = nullptr;
+    w.accums.clear();
+    // (none of these calls holds g_accum_mu while it waits for the world's lock)
+    g_accum_cv.wait(g, [&] { return w.accum_calls == 0; });
 }
 
 AccumState *accum_create(WorldState &w, size_t width, size_t height, uint32_t stride, int32_t depth,

@@ -239,6 +239,9 @@ long rt_read_samples(const Rust_WorldHandle *h, int device, float *out, size_t n
 
 void rt_free_world(Rust_WorldHandle *h) {
     if (!h) return;
+    // (calls on the world's accumulators that other threads are in return first;
+    // later ones fail: they read the handle's camera and take the world's lock)
+    if (h->world) rtamd::world_retire(h->world->state);
     delete h->world;
     delete h->camera;
     delete h;
@@ -427,48 +430,69 @@ RtAccum *rt_accum_create(const Rust_WorldHandle *h, size_t width, size_t height,
     return st ? new RtAccum{h, st} : nullptr;
 }
 
-// the accumulator's current camera, or nullptr (with the error set)
-static const rtamd::CameraModel *accum_camera(const RtAccum *acc, const char *who) {
-    if (!acc || !acc->state) {
-        rtamd::set_error(std::string(who) + ": null accumulator");
-        return nullptr;
+// One call on an accumulator: keeps the accumulator's world alive until it
+// returns (rt_free_world on another thread waits for it, runtime.h accum_enter)
+// and gives the handle's current camera.  False, with the error set, for a null
+// accumulator and after the world was freed: the freed handle is not touched.
+namespace {
+class AccumCall {
+public:
+    AccumCall(const RtAccum *acc, const char *who) {
+        if (!acc || !acc->state) {
+            rtamd::set_error(std::string(who) + ": null accumulator");
+            return;
+        }
+        world_ = rtamd::accum_enter(*acc->state);
+        if (!world_) {
+            rtamd::set_error(std::string(who) + ": the accumulator's world was freed");
+            return;
+        }
+        if (!acc->handle->camera) {
+            rtamd::set_error(std::string(who) + ": null camera");
+            return;
+        }
+        cam_ = &acc->handle->camera->cam;
     }
-    if (!acc->state->world) {
-        rtamd::set_error(std::string(who) + ": the accumulator's world was freed");
-        return nullptr;
+    ~AccumCall() {
+        if (world_) rtamd::accum_leave(world_);
     }
-    if (!acc->handle->camera) {
-        rtamd::set_error(std::string(who) + ": null camera");
-        return nullptr;
-    }
-    return &acc->handle->camera->cam;
-}
+    AccumCall(const AccumCall &) = delete;
+    AccumCall &operator=(const AccumCall &) = delete;
+    explicit operator bool() const { return cam_ != nullptr; }
+    const rtamd::CameraModel &cam() const { return *cam_; }
+
+private:
+    rtamd::WorldState *world_ = nullptr;
+    const rtamd::CameraModel *cam_ = nullptr;
+};
+}  // namespace
 
 int rt_accum_add(RtAccum *acc, int64_t nsamples, Rust_ColorU8 *pixels, RtRenderStats *stats) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_add");
-    if (!cam) return -1;
-    return rtamd::accum_add(*acc->state, *cam, nsamples, nullptr, nullptr, pixels, stats);
+    const AccumCall call(acc, "rt_accum_add");
+    if (!call) return -1;
+    return rtamd::accum_add(*acc->state, call.cam(), nsamples, nullptr, nullptr, pixels, stats);
 }
 
 int rt_accum_add_device(RtAccum *acc, int64_t nsamples, void *d_rgba, void *hip_stream, RtRenderStats *stats) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_add_device");
-    if (!cam) return -1;
-    return rtamd::accum_add(*acc->state, *cam, nsamples, static_cast<uint32_t *>(d_rgba),
+    const AccumCall call(acc, "rt_accum_add_device");
+    if (!call) return -1;
+    return rtamd::accum_add(*acc->state, call.cam(), nsamples, static_cast<uint32_t *>(d_rgba),
                             static_cast<hipStream_t>(hip_stream), nullptr, stats);
 }
 
 long rt_accum_samples(RtAccum *acc) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_samples");
-    return cam ? rtamd::accum_samples(*acc->state, *cam) : -1;
+    const AccumCall call(acc, "rt_accum_samples");
+    return call ? rtamd::accum_samples(*acc->state, call.cam()) : -1;
 }
 
 int rt_accum_read(RtAccum *acc, float *sums) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_accum_read");
-    return cam ? rtamd::accum_read(*acc->state, *cam, sums) : -1;
+    const AccumCall call(acc, "rt_accum_read");
+    return call ? rtamd::accum_read(*acc->state, call.cam(), sums) : -1;
 }
 
 int rt_accum_reset(RtAccum *acc) {
-    if (!accum_camera(acc, "rt_accum_reset")) return -1;
+    const AccumCall call(acc, "rt_accum_reset");
+    if (!call) return -1;
     return rtamd::accum_reset(*acc->state);
 }
 
@@ -499,34 +523,34 @@ int rt_adapt_enable(RtAccum *acc, const RtAdaptOptions *opts) {
         rtamd::set_error("rt_adapt_enable: min_samples must be at least 2");
         return -1;
     }
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_enable");
-    if (!cam) return -1;
-    return rtamd::adapt_enable(*acc->state, *cam, o.tolerance, o.bias, o.min_samples);
+    const AccumCall call(acc, "rt_adapt_enable");
+    if (!call) return -1;
+    return rtamd::adapt_enable(*acc->state, call.cam(), o.tolerance, o.bias, o.min_samples);
 }
 
 int rt_adapt_disable(RtAccum *acc) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_disable");
-    return cam ? rtamd::adapt_disable(*acc->state, *cam) : -1;
+    const AccumCall call(acc, "rt_adapt_disable");
+    return call ? rtamd::adapt_disable(*acc->state, call.cam()) : -1;
 }
 
 long rt_adapt_active(RtAccum *acc) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_active");
-    return cam ? rtamd::adapt_active(*acc->state, *cam) : -1;
+    const AccumCall call(acc, "rt_adapt_active");
+    return call ? rtamd::adapt_active(*acc->state, call.cam()) : -1;
 }
 
 int rt_adapt_read_counts(RtAccum *acc, uint32_t *counts) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_read_counts");
-    return cam ? rtamd::adapt_read_counts(*acc->state, *cam, counts) : -1;
+    const AccumCall call(acc, "rt_adapt_read_counts");
+    return call ? rtamd::adapt_read_counts(*acc->state, call.cam(), counts) : -1;
 }
 
 int rt_adapt_read_sumsq(RtAccum *acc, float *sumsq) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_read_sumsq");
-    return cam ? rtamd::adapt_read_sumsq(*acc->state, *cam, sumsq) : -1;
+    const AccumCall call(acc, "rt_adapt_read_sumsq");
+    return call ? rtamd::adapt_read_sumsq(*acc->state, call.cam(), sumsq) : -1;
 }
 
 long rt_adapt_read_active(RtAccum *acc, uint32_t *list, size_t cap) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_adapt_read_active");
-    return cam ? rtamd::adapt_read_active(*acc->state, *cam, list, cap) : -1;
+    const AccumCall call(acc, "rt_adapt_read_active");
+    return call ? rtamd::adapt_read_active(*acc->state, call.cam(), list, cap) : -1;
 }
 
 // ---- first-hit records
@@ -610,16 +634,16 @@ int rt_filter_run(RtFilter *f, const RtFilterOptions *opts, const float *rgb, co
 }
 
 int rt_filter_accum(RtAccum *acc, const RtFilterOptions *opts, float *out_rgb, Rust_ColorU8 *pixels) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_filter_accum");
-    if (!cam) return -1;
-    return rtamd::filter_accum(acc->state, cam, opts, out_rgb, pixels, false, nullptr, "rt_filter_accum");
+    const AccumCall call(acc, "rt_filter_accum");
+    if (!call) return -1;
+    return rtamd::filter_accum(acc->state, &call.cam(), opts, out_rgb, pixels, false, nullptr, "rt_filter_accum");
 }
 
 int rt_filter_accum_device(RtAccum *acc, const RtFilterOptions *opts, float *d_out_rgb, void *d_rgba,
                            void *hip_stream) {
-    const rtamd::CameraModel *cam = accum_camera(acc, "rt_filter_accum_device");
-    if (!cam) return -1;
-    return rtamd::filter_accum(acc->state, cam, opts, d_out_rgb, d_rgba, true, static_cast<hipStream_t>(hip_stream),
+    const AccumCall call(acc, "rt_filter_accum_device");
+    if (!call) return -1;
+    return rtamd::filter_accum(acc->state, &call.cam(), opts, d_out_rgb, d_rgba, true, static_cast<hipStream_t>(hip_stream),
                                "rt_filter_accum_device");
 }
 

@@ -209,6 +209,9 @@ int filter_accum(AccumState *ap, const CameraModel *cam, const RtFilterOptions *
     }
     FilterState &f = *a.filter;
     std::lock_guard<std::mutex> flock(f.mu);
+    // d->done is recorded again below, on s: it must still stand for the frame
+    // another stream may be running, which the next frame on s has to wait for
+    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
     // after the accumulator's last pass, like its other readers
     if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
 

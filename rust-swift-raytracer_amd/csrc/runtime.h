@@ -231,6 +231,9 @@ struct WorldState {
     // the accumulators created on this world (accum_create / accum_free);
     // the world's destructor detaches them, after which their calls fail
     std::vector<AccumState *> accums;
+    // calls on those accumulators that are under way (accum_enter / accum_leave):
+    // world_retire, before the world is freed, waits until there are none
+    uint32_t accum_calls = 0;
     // one frame at a time per handle: calls from several host threads are
     // serialised here (render_frame_multi re-enters render_frame)
     std::recursive_mutex mu;
@@ -366,6 +369,14 @@ long accum_samples(AccumState &a, const CameraModel &cam);
 int accum_read(AccumState &a, const CameraModel &cam, float *sums);
 int accum_reset(AccumState &a);
 void accum_free(AccumState *a);
+// A call on an accumulator from the C ABI: accum_enter returns the accumulator's
+// world (nullptr: it was freed) and keeps it from being freed until accum_leave.
+// world_retire detaches the world's accumulators, so that their later calls fail,
+// and waits for the calls under way on other threads; rt_free_world calls it
+// before it deletes the world and the handle those calls read.
+WorldState *accum_enter(AccumState &a);
+void accum_leave(WorldState *w);
+void world_retire(WorldState &w);
 // Adaptive accumulation (rt_adapt_*, include/raytracer_amd.h).  enable and
 // disable need an accumulator that holds no samples; the reads wait for the
 // last pass.  read_active returns the list's length (list may be nullptr).
