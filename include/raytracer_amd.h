@@ -529,6 +529,17 @@ int rt_leaf_defer(const Rust_WorldHandle *handle, int device);
  * bit-identical frames.  Negative: an error. */
 int rt_trace_plain(const Rust_WorldHandle *handle, int device);
 
+/* Diagnostics: the number of image rows the last frame launch on `device`
+ * (-1 = current) rendered with the sky kernel instead of the trace kernel:
+ * rows at the top and the bottom of the image none of whose primary rays can
+ * hit a sphere (one rank, COUNTER, a sphere-only scene with primary sphere
+ * lists, fused resolve, no stats, depth >= 1; RT_AMD_SKY_ROWS=0 turns it
+ * off).  The rows are classified on the host once the first frame of a camera
+ * and frame size is enqueued, so that frame still traces every row.  0 when
+ * every row was traced.  Both give bit-identical frames.
+ * Negative: an error. */
+int rt_sky_rows(const Rust_WorldHandle *handle, int device);
+
 /* Diagnostics: which trace-kernel instances were launched on `device` (-1 =
  * current) since the set was last cleared -- by frames, accumulation and
  * adaptive passes and the passes of a SERIAL frame.  The library compiles one

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <thread>
 
@@ -1041,6 +1042,191 @@ bool sphere_list_params(const SphereBVH &bv, const CameraModel &cam, size_t widt
     out.width = (uint32_t)width;
     out.height = (uint32_t)height;
     return true;
+}
+
+// ---- sky rows (bvh.h classify_sky_rows)
+namespace {
+
+// Tree sphere i's pixel rectangle by build_primary_sphere_lists' arithmetic
+// (the same double operations in its order).  0: entirely behind the camera or
+// off the image (in no list), 1: cols [c0, c1] x rows [r0, r1] (rows from the
+// bottom), -1: no lists at all (non-finite, or it straddles the camera plane).
+int sphere_list_rect(const SphereBVH &bv, uint32_t i, const SphereListParams &sp, int64_t rect[4]) {
+    const float *s = &bv.prims[(size_t)i * 4];
+    const double *o = sp.o;
+    const double c[3] = {s[0], s[1], s[2]};
+    const double r = std::sqrt((double)s[3]) * (1 + 1e-6);
+    const double a = std::sqrt((c[0] - o[0]) * (c[0] - o[0]) + (c[1] - o[1]) * (c[1] - o[1]) +
+                               (c[2] - o[2]) * (c[2] - o[2]));
+    const double R = r + 2 * 3e-3 * (a + r) * 1.01 + 2 * sp.e_abs;
+    if (!std::isfinite(R) || !std::isfinite(a)) return -1;
+    double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
+    int front = 0, behind = 0;
+    for (int k = 0; k < 8; ++k) {
+        const double P[3] = {c[0] + (k & 1 ? R : -R) - o[0], c[1] + (k & 2 ? R : -R) - o[1],
+                             c[2] + (k & 4 ? R : -R) - o[2]};
+        double w[3];
+        for (int q = 0; q < 3; ++q) w[q] = sp.Mi[3 * q] * P[0] + sp.Mi[3 * q + 1] * P[1] + sp.Mi[3 * q + 2] * P[2];
+        const double wn = std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]);
+        if (w[2] > 1e-6 * wn) {
+            ++front;
+            umin = std::min(umin, w[0] / w[2]); umax = std::max(umax, w[0] / w[2]);
+            vmin = std::min(vmin, w[1] / w[2]); vmax = std::max(vmax, w[1] / w[2]);
+        } else if (w[2] < -1e-6 * wn) {
+            ++behind;
+        }
+    }
+    if (behind == 8) return 0;
+    if (front < 8) return -1;
+    const int64_t W = sp.width, H = sp.height;
+    const double cl = std::floor(umin * sp.wden) - 2, ch = std::floor(umax * sp.wden) + 1;
+    const double rl = std::floor(vmin * sp.hden) - 2, rh = std::floor(vmax * sp.hden) + 1;
+    if (ch < 0 || cl > (double)(W - 1) || rh < 0 || rl > (double)(H - 1)) return 0;
+    rect[0] = std::max<int64_t>(0, (int64_t)cl); rect[1] = std::min<int64_t>(W - 1, (int64_t)ch);
+    rect[2] = std::max<int64_t>(0, (int64_t)rl); rect[3] = std::min<int64_t>(H - 1, (int64_t)rh);
+    return 1;
+}
+
+// A big sphere against the primary rays of the rectangle u in [u0, u1], v in
+// [v0, v1] of the camera map D(u, v) = L + h u + vv v: true
+// when none of them can make Sphere::hit return a hit.  oc = origin - centre,
+// kappa = |oc|^2 - r^2 - E > 0, away = the bound on |f32 half_b - oc.d| per
+// unit of |D|.  A ray with half_b > 0 in f32 has two negative roots, so only
+// the part of the rectangle with oc.D <= away max|D| matters: the rectangle
+// clipped by that half-plane (oc.D is linear in u, v), a convex polygon.  On
+// it g = (oc.D)^2 - kappa |D|^2, a quadratic in (u, v), must be negative: its
+// maximum lies at a vertex of the polygon, at the stationary point of an edge
+// or at the interior one, all tried here.
+bool big_sphere_clear(const double oc[3], double kappa, double away, const double L[3], const double h[3],
+                      const double vv[3], double u0, double u1, double v0, double v1) {
+    const double *c[3] = {h, vv, L};
+    double ac[3], Q[3][3], G[3][3];
+    for (int i = 0; i < 3; ++i) ac[i] = oc[0] * c[i][0] + oc[1] * c[i][1] + oc[2] * c[i][2];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            G[i][j] = c[i][0] * c[j][0] + c[i][1] * c[j][1] + c[i][2] * c[j][2];
+            Q[i][j] = ac[i] * ac[j] - kappa * G[i][j];
+        }
+    struct P2 { double u, v; };
+    const P2 rect[4] = {{u0, v0}, {u1, v0}, {u1, v1}, {u0, v1}};
+    double max_len = 0;  // (|D| is convex: its maximum is at a corner)
+    for (const P2 &p : rect)
+        max_len = std::max(max_len, std::sqrt(G[0][0] * p.u * p.u + G[1][1] * p.v * p.v + G[2][2] +
+                                              2 * (G[0][1] * p.u * p.v + G[0][2] * p.u + G[1][2] * p.v)));
+    const double lim = away * max_len;
+    auto toward = [&](const P2 &p) { return lim - (ac[0] * p.u + ac[1] * p.v + ac[2]); };  // >= 0: kept
+    P2 poly[8];
+    int n = 0;
+    for (int k = 0; k < 4; ++k) {  // the rectangle clipped by toward >= 0
+        const P2 &p = rect[k], &q = rect[(k + 1) & 3];
+        const double tp = toward(p), tq = toward(q);
+        if (tp >= 0) poly[n++] = p;
+        if ((tp >= 0) != (tq >= 0)) {
+            const double t = tp / (tp - tq);
+            poly[n++] = P2{p.u + t * (q.u - p.u), p.v + t * (q.v - p.v)};
+        }
+    }
+    if (n == 0) return !std::isnan(lim + toward(rect[0]));  // every ray points away
+    auto g = [&](const P2 &p) {
+        return Q[0][0] * p.u * p.u + Q[1][1] * p.v * p.v + Q[2][2] +
+               2 * (Q[0][1] * p.u * p.v + Q[0][2] * p.u + Q[1][2] * p.v);
+    };
+    double m = -1e300;
+    for (int k = 0; k < n; ++k) {
+        const P2 &p = poly[k], &q = poly[(k + 1) % n];
+        const P2 mid{0.5 * (p.u + q.u), 0.5 * (p.v + q.v)};
+        const double g0 = g(p), gh = g(mid), g1 = g(q);
+        m = std::max({m, g0, gh, g1});
+        if (std::isnan(g0 + gh + g1)) return false;
+        // g along the edge is A t^2 + B t + g0
+        const double A = 2 * (g1 + g0 - 2 * gh), B = g1 - g0 - A;
+        if (A < 0) {
+            const double t = -B / (2 * A);
+            if (t > 0 && t < 1) m = std::max(m, g(P2{p.u + t * (q.u - p.u), p.v + t * (q.v - p.v)}));
+        }
+    }
+    const double det = Q[0][0] * Q[1][1] - Q[0][1] * Q[0][1];
+    if (det != 0) {
+        const P2 s{(Q[0][1] * Q[1][2] - Q[1][1] * Q[0][2]) / det, (Q[0][1] * Q[0][2] - Q[0][0] * Q[1][2]) / det};
+        if (s.u > u0 && s.u < u1 && s.v > v0 && s.v < v1 && toward(s) >= 0) m = std::max(m, g(s));
+    }
+    return m < 0;  // (NaN: not clear)
+}
+
+}  // namespace
+
+SkyRows classify_sky_rows(const SphereBVH &bv, const std::vector<Sphere> &spheres, const CameraModel &cam,
+                          size_t width, size_t height) {
+    SphereListParams sp;
+    if (!sphere_list_params(bv, cam, width, height, sp)) return SkyRows{};
+    for (const Sphere &s : spheres)
+        if (!finite_sphere(s) || !std::isfinite(s.radius * s.radius)) return SkyRows{};
+    const int64_t W = (int64_t)width, H = (int64_t)height;
+    std::vector<uint8_t> covered(height, 0);  // by row from the bottom
+    for (uint32_t i = 0; i < sp.n; ++i) {
+        int64_t rect[4];
+        const int rc = sphere_list_rect(bv, i, sp, rect);
+        if (rc < 0) return SkyRows{};
+        if (rc > 0) std::fill(covered.begin() + rect[2], covered.begin() + rect[3] + 1, (uint8_t)1);
+    }
+    // the rows at either end that no list rectangle covers ...
+    int64_t top = 0, bottom = 0;
+    while (top < H && !covered[H - 1 - top]) ++top;
+    while (top + bottom < H && !covered[bottom]) ++bottom;
+    // ... and of those, the rows every big sphere is clear of
+    if (!bv.big.empty() && top + bottom > 0) {
+        // the rounding of u, v and of the two normalised directions moves a ray
+        // by e_dir at most; it must stay within half a pixel pitch of its exact
+        // footprint (the other half covers draw_plus and the divisions)
+        const Vec3 cv[4] = {cam.origin, cam.lower_left, cam.horizontal, cam.vertical};
+        double S = 0;
+        for (const Vec3 &v : cv) S += std::fabs((double)v.x) + std::fabs((double)v.y) + std::fabs((double)v.z);
+        const double e_dir = 0x1p-20 * S;  // 16 u S, u = 2^-24
+        double eps[3];
+        for (int q = 0; q < 3; ++q)
+            eps[q] = e_dir * (std::fabs(sp.Mi[3 * q]) + std::fabs(sp.Mi[3 * q + 1]) + std::fabs(sp.Mi[3 * q + 2]));
+        if (!(eps[2] < 0.25)) return SkyRows{};
+        const double du = (eps[0] + 2 * eps[2]) / (1 - eps[2]), dv = (eps[1] + 2 * eps[2]) / (1 - eps[2]);
+        if (!(du <= 0.5 / sp.wden) || !(dv <= 0.5 / sp.hden)) return SkyRows{};
+        const double o[3] = {cam.origin.x, cam.origin.y, cam.origin.z};
+        const double L[3] = {cam.lower_left.x - o[0], cam.lower_left.y - o[1], cam.lower_left.z - o[2]};
+        const double h[3] = {cam.horizontal.x, cam.horizontal.y, cam.horizontal.z};
+        const double vv[3] = {cam.vertical.x, cam.vertical.y, cam.vertical.z};
+        const double u0 = -1.0 / sp.wden, u1 = (double)(W + 1) / sp.wden;
+        for (uint32_t id : bv.big) {
+            const Sphere &s = spheres[id];
+            const double oc[3] = {o[0] - s.center.x, o[1] - s.center.y, o[2] - s.center.z};
+            const double N = oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2];
+            const double E = 0x1p-18 * N;  // twice the f32 bound 32 u |oc|^2
+            const double kappa = N - (double)s.radius * (double)s.radius - E;
+            if (!(kappa > 0) || !(N < 1e30)) return SkyRows{};  // the camera inside or within E of it
+            const double away = 0x1p-20 * std::sqrt(N);
+            // rows [lo, hi) from the bottom at once: their footprints' union, widened
+            auto clear = [&](int64_t lo, int64_t hi) {
+                return big_sphere_clear(oc, kappa, away, L, h, vv, u0, u1, (double)(lo - 1) / sp.hden,
+                                        (double)(hi + 1) / sp.hden);
+            };
+            // the clear rows at the top end (or the bottom end) of [lo, hi): whole
+            // blocks first, halves where a block is not clear -- a clear block's
+            // rows are clear one by one, so this is the row-by-row count
+            std::function<int64_t(int64_t, int64_t, bool)> run = [&](int64_t lo, int64_t hi, bool from_top) -> int64_t {
+                if (lo >= hi) return 0;
+                if (clear(lo, hi)) return hi - lo;
+                if (hi - lo == 1) return 0;
+                const int64_t mid = (lo + hi) / 2;
+                const int64_t a0 = from_top ? mid : lo, a1 = from_top ? hi : mid;  // the half at that end
+                const int64_t n = run(a0, a1, from_top);
+                if (n < a1 - a0) return n;
+                return n + (from_top ? run(lo, mid, true) : run(mid, hi, false));
+            };
+            top = run(H - top, H, true);
+            bottom = run(0, std::min(bottom, H - top), false);
+        }
+    }
+    SkyRows out;
+    out.top = (uint32_t)top;
+    out.bottom = (uint32_t)std::min(bottom, H - top);
+    return out;
 }
 
 PrimarySphereLists build_primary_sphere_lists(const SphereBVH &bv, const CameraModel &cam,

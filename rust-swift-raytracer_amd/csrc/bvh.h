@@ -229,4 +229,19 @@ struct SphereListParams {
 bool sphere_list_params(const SphereBVH &bv, const CameraModel &cam, size_t width, size_t height,
                         SphereListParams &out);
 
+// Sky rows: image rows none of whose primary rays can make any
+// sphere's Sphere::hit (common.rs:59-98) return a hit, so every sample of
+// theirs is the background.  top: that many rows from the image's top edge,
+// bottom: from its bottom edge (top + bottom <= height; sky rows in between
+// are not reported).  Tree spheres: a row is clear when no sphere's list
+// rectangle (build_primary_sphere_lists) covers it, under sphere_list_params'
+// preconditions.  Big spheres (bv.big): the exact discriminant, in double,
+// over the row's footprints widened by a pixel pitch, against the f32
+// evaluation error E.  No rows where the lists are not built, where the
+// camera is inside or within E of a big sphere, or where any sphere is
+// non-finite (or its squared radius is).  spheres: the scene's, in file order.
+struct SkyRows { uint32_t top = 0, bottom = 0; };
+SkyRows classify_sky_rows(const SphereBVH &bv, const std::vector<Sphere> &spheres, const CameraModel &cam,
+                          size_t width, size_t height);
+
 }  // namespace rtamd

@@ -211,6 +211,14 @@ int rt_trace_plain(const Rust_WorldHandle *h, int device) {
     return rtamd::trace_plain(h->world->state, device);
 }
 
+int rt_sky_rows(const Rust_WorldHandle *h, int device) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_sky_rows: null argument");
+        return -1;
+    }
+    return rtamd::sky_rows(h->world->state, device);
+}
+
 int rt_leaf_defer(const Rust_WorldHandle *h, int device) {
     if (!h || !h->world) {
         rtamd::set_error("rt_leaf_defer: null argument");

@@ -129,6 +129,8 @@ struct FrameValues {
     const uint4 *corner_img = nullptr; // the LDS tree as corner records (sphere-only frames), else box records
     TraceRequest want;                 // ... and what every launch asks for (render.h; kind: choose_kernel_instance)
     bool primary_lists = false;        // the frame's primary rays use candidate lists (spheres or triangles)
+    SkyRows dev_sky;                   // ... and, with the device's lists, the sky rows classified with them
+    SkyRows sky;                       // the rows this frame gives the sky kernel (choose_sky_rows; none: all traced)
     bool use_tbvh = false;             // bind_triangle_search
     int ptl_where = 0;                 // rt_primary_tri_lists: 0 none, 1 host build, 2 device build
     float inv_spp = 0.0f;
@@ -269,6 +271,7 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
             if (rc) return rc;
             p.spl = ok ? d->gspl.lists.get() : nullptr;
             f.primary_lists = ok;
+            if (ok) f.dev_sky = d->gspl.sky;
         } else if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 &&
                    prepare_primary_sphere_lists(w, cam, width, height)) {
             if (d->spl_version != w.spl_version) {
@@ -455,6 +458,21 @@ int choose_kernel_instance(DeviceState *d, const SerialPass *sp, const AccumPass
     return 0;
 }
 
+// The rows the frame renders with the sky kernel: those the
+// lists' build classified, for a frame whose every traced sample of such a row
+// would be the background and nothing else -- COUNTER, one rank, a sphere-only
+// scene searched by the tree with primary lists, fused resolve, no counters,
+// no pass, depth >= 1 (a frame of depth <= 0 is black).  RT_AMD_SKY_ROWS=0:
+// every row is traced (A/B runs and tests).
+void choose_sky_rows(const DeviceState *d, const SerialPass *sp, const AccumPass *ap, FrameValues &f,
+                     const TraceParams &p) {
+    f.sky = SkyRows{};
+    if (sp || ap || f.timed || !f.fused || f.replay || f.nranks != 1 || d->ntri != 0 || !f.use_bvh ||
+        !f.primary_lists || p.depth < 1 || p.ablate != 0 || env_u64("RT_AMD_SKY_ROWS", 1) == 0)
+        return;
+    f.sky = f.dev_sky;
+}
+
 // launch_trace, with the instance it ran noted in the device's set (rt_trace_launched)
 hipError_t launch_recorded(DeviceState *d, TraceVariant v, const TraceParams &p, const TraceTail &tail,
                            uint32_t blocks, hipStream_t s) {
@@ -571,8 +589,14 @@ LaunchPlan plan_launch(DeviceState *d, const TraceParams &p, const FrameValues &
         // wave at 8,192 waves) on 4-pixel chunks: lean frame 3.900 ms
         // against 3.745 ms with 8, 3.811 with 12 and 3.912 with 16 pixels
         // (profiles/round5_walk/ab_c2_chunk.jsonl); the 8-rank tile keeps
-        // 4 px (0.678 ms, 8 px 0.849 ms)
-        while (px > 4 && njobs / (nwaves * px * spp) < 16) px /= 2;
+        // 4 px (0.678 ms, 8 px 0.849 ms).  The C2 launch without its 535 sky
+        // rows has 15.97 chunks of 8 px per wave and takes
+        // 4 px by this rule: 2.929 ms against 2.917 with 8 px, inside either
+        // variant's spread of 0.03 (profiles/sky_rows/ab_c2.jsonl, new against
+        // new8px, RT_AMD_CHUNKS_PER_WAVE=15; C3 has 250 chunks per wave either
+        // way), so the rule stays at 16 for that launch too
+        const uint64_t min_chunks = env_u64("RT_AMD_CHUNKS_PER_WAVE", 16);
+        while (px > 4 && njobs / (nwaves * px * spp) < min_chunks) px /= 2;
         chunk = std::max<uint64_t>(chunk, px * spp);
     }
     // job-queue partitions: each keeps >= 16 chunks.  Whole-walk
@@ -623,9 +647,16 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
     const size_t units_per_slab =
         adapt ? (size_t)std::min<uint64_t>(std::max<uint64_t>(1, f.slab_jobs / spp), std::max<size_t>(units, 1))
               : f.rows_per_slab;
+    // the sky rows first, in their own kernel on the same stream: the trace
+    // launches take the rows between the two blocks (none: no trace launch, and
+    // rt_trace_plain, rt_leaf_defer and rt_trace_launched keep saying what the
+    // last trace launch ran)
+    const size_t row_lo = f.sky.top, row_hi = units - f.sky.bottom;
+    d->last_sky_rows = f.sky.top + f.sky.bottom;
+    if (d->last_sky_rows) HIP_TRY(launch_sky_rows(p, f.sky.top, f.sky.bottom, s));
     uint32_t &nslab = done.nslab;  // (counted frames: event triple per launch)
-    for (size_t r0 = 0; r0 < units; r0 += units_per_slab, ++nslab) {
-        const size_t rows = std::min(units_per_slab, units - r0);
+    for (size_t r0 = row_lo; r0 < row_hi; r0 += units_per_slab, ++nslab) {
+        const size_t rows = std::min(units_per_slab, row_hi - r0);
         hipEvent_t *ev3 = nullptr;
         if (timed) {
             while (d->tev.size() < 3 * (size_t)(nslab + 1)) {
@@ -796,10 +827,12 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     rc = choose_kernel_instance(d, sp, ap, s, f, p);
     if (rc) return rc;
     if (sp) return launch_serial_pass(d, width, height, o, sp, s, f, p);
+    choose_sky_rows(d, sp, ap, f, p);
 
     LaunchesDone done;
     rc = enqueue_launches(d, width, height, d_out, ap, s, f, p, done);
     if (rc) return rc;
+    classify_pending_sky_rows(w, d);  // (for the next frame, while the device runs this one)
     // without stats the frame stays asynchronous on the stream (no host wait)
     if (!f.timed) return 0;
     rc = queue_frame_stats(d, s, f, p, done);
@@ -903,6 +936,14 @@ int trace_plain(WorldState &w, int device) {
     int rc = device_for(w, device, d);
     if (rc) return rc;
     return d->last_plain ? 1 : 0;
+}
+
+int sky_rows(WorldState &w, int device) {
+    std::lock_guard<std::recursive_mutex> lock(w.mu);  // (device_for may add a device)
+    DeviceState *d = nullptr;
+    int rc = device_for(w, device, d);
+    if (rc) return rc;
+    return (int)d->last_sky_rows;
 }
 
 int trace_launched(WorldState &w, int device, uint8_t *out, size_t n, bool clear) {

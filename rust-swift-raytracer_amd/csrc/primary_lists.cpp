@@ -119,10 +119,27 @@ int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel &cam, s
                 }
             }
         }
+        // the frame's sky rows go with the lists: classified on the host once this
+        // frame is enqueued (classify_pending_sky_rows), so its launches do not
+        // wait for that; until then there are none
+        g.sky = SkyRows{};
+        g.sky_pending = g.ok;
         g.remember(cam, width, height);
     }
     ok = g.ok;
     return 0;
+}
+
+// The sky rows of the device's current lists (bvh.h classify_sky_rows; some
+// tens of microseconds of host arithmetic at 1080p), where a rebuild left them
+// to be done: called once a frame's launches are enqueued, so the work hides
+// behind the frame and the first frame after a camera move starts no later
+// than without it.  The next frame finds them.
+void classify_pending_sky_rows(WorldState &w, DeviceState *d) {
+    auto &g = d->gspl;
+    if (!g.sky_pending) return;
+    g.sky = classify_sky_rows(w.bvh, w.scene.spheres, g.cam, g.w, g.h);
+    g.sky_pending = false;
 }
 
 // Primary triangle strip lists are built on the device too (RT_AMD_GPU_TRI_LISTS,

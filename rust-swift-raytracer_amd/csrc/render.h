@@ -355,6 +355,14 @@ struct FirstHitTail {
     uint32_t view;
 };
 hipError_t launch_first_hit(const TraceParams &p, const FirstHitTail &tail, hipStream_t stream);
+// The frame's sky rows (sky.hip sky_rows_kernel): the first
+// `top` and the last `bottom` image rows of a one-rank COUNTER frame of depth
+// >= 1, whose primary rays can hit nothing (bvh.h classify_sky_rows).  One lane
+// per pixel runs the pixel's p.spp samples in order -- seed (the reference's
+// job index, 64-bit), draws, camera ray, background -- folds them and stores
+// the RGBA8 word at p.out, as the trace kernel's fused resolve would.  p: the
+// frame's, as launch_trace gets it (camera, divisions, seed, inv_spp, alpha).
+hipError_t launch_sky_rows(const TraceParams &p, uint32_t top, uint32_t bottom, hipStream_t stream);
 // The edge-aware filter (filter.hip; DESIGN.md 5.9, include/raytracer_amd.h
 // rt_filter_*).  pack: one lane per pixel writes col[i] = {r, g, b, (r + g) + b}
 // and, from the 32-byte first-hit records, g0[i] = {normal, prim bits} and

@@ -80,6 +80,8 @@ struct DeviceState {
         CameraModel cam{};
         size_t w = 0, h = 0;
         bool built = false, ok = false;
+        SkyRows sky;                                           // the lists' sky rows (none without lists) ...
+        bool sky_pending = false;                              // ... still to be classified (classify_pending_sky_rows)
         bool current(const CameraModel &c, size_t width, size_t height) const {
             return built && w == width && h == height && std::memcmp(&cam, &c, sizeof(c)) == 0;
         }
@@ -193,6 +195,7 @@ struct DeviceState {
     bool last_fused = false;                                    // it resolved in-kernel (no slab)
     int last_leaf_defer = 0;                                    // its walk's pending leaves per lane (rt_leaf_defer)
     bool last_plain = false;                                    // it ran the plain instance (rt_trace_plain)
+    uint32_t last_sky_rows = 0;                                 // rows the last frame launch gave the sky kernel (rt_sky_rows)
     // the instances launched on this device since the last clear, one byte per
     // render.h trace_key (rt_trace_launched): frames, passes and SERIAL passes
     uint8_t trace_launched[kTraceKeys] = {};
@@ -452,6 +455,7 @@ void prepare_camera(WorldState &w, const CameraModel &cam, bool tree = false);
 long read_samples(WorldState &w, int device, float *out, size_t n);
 int leaf_defer(WorldState &w, int device);
 int trace_plain(WorldState &w, int device);
+int sky_rows(WorldState &w, int device);
 // the device's set of launched instances into out (n bytes at most, one per
 // render.h trace_key; out may be null), cleared afterwards when asked -> kTraceKeys
 // (rt_trace_launched)

@@ -73,6 +73,7 @@ void prepare_camera_lists(WorldState &w, const CameraModel &cam, size_t width, s
 bool prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height);
 int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
                         hipStream_t s, bool &ok);
+void classify_pending_sky_rows(WorldState &w, DeviceState *d);
 int device_tri_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
                      hipStream_t s, bool &ok);
 
