@@ -505,6 +505,114 @@ int rt_filter_accum(RtAccum *acc, const RtFilterOptions *opts, float *out_rgb,
 int rt_filter_accum_device(RtAccum *acc, const RtFilterOptions *opts, float *d_out_rgb,
                            void *d_rgba, void *hip_stream);
 
+/* ---- Temporal reprojection: an accumulator's result carried across camera
+ * moves.
+ *
+ * An accumulator starts over on every camera move; its history does not.  A
+ * history belongs to one accumulator and holds two snapshots, cur and prev, of
+ * resolved views.  A snapshot is, per pixel of the accumulator's frame, top row
+ * first, a colour with a length {r, g, b, len} (f32: len is the number of
+ * samples the colour stands for) and a guide {position.xyz, prim} from the
+ * first-hit records it was made with; plus the 12 camera floats and the scene
+ * edit version it was made under.  A snapshot is valid or not.
+ *
+ * Every step below is one rounded f32 operation, unfused; divisions are
+ * correctly rounded; comparisons are false for NaN; only + - * /, fabs, floor,
+ * sqrt and compares appear.
+ *
+ * rt_history_resolve on an accumulator that holds n_p samples per pixel (the
+ * samples held, or count[p] on an adaptive accumulator):
+ *   1. The accumulator's reset rule is applied first, as by rt_filter_accum:
+ *      "no samples held" and "the accumulator's world was freed" are errors.
+ *   2. A snapshot made under another scene edit version: both become invalid.
+ *   3. cur valid and its camera differs on bits from the accumulator's camera
+ *      C: cur and prev swap (the old cur is the new prev).  Else prev stays.
+ *   4. The accumulator's first-hit records g are made current (rt_filter_accum's
+ *      cache: su = sv = 0.5, the accumulator's accel, camera C).
+ *   5. Per pixel p:  inv = 1.0f / (float)n_p;  m_k = sum_k * inv;  nf = (float)n_p.
+ *      No history if prev is invalid or prim_p == 0 (sky takes none).  Else, with
+ *      prev's camera O, L, H, V (origin, lower-left corner, horizontal, vertical)
+ *      and P = position_p:
+ *        A = L - O;  d = P - O;  n0 = H x V;  n1 = V x A;  n2 = A x H
+ *          (a x b = (a.y*b.z - a.z*b.y, -(a.x*b.z - a.z*b.x), a.x*b.y - a.y*b.x),
+ *           maths.rs:88-94, each product rounded before the subtraction)
+ *        dot3(a, b) = ((a.x*b.x) + (a.y*b.y)) + (a.z*b.z)
+ *        det = dot3(A, n0);  s = dot3(d, n0);  a = dot3(d, n1);  b = dot3(d, n2)
+ *        unless (s > 0 && det > 0) || (s < 0 && det < 0): no history (behind)
+ *        u = a / s;  v = b / s
+ *        fx = u * (float)(width - 1) - 0.5f;  fy = v * (float)(height - 1) - 0.5f
+ *          (fy counts rows from the bottom, as v does in cast_ray)
+ *        unless fx > -1 && fx < (float)width && fy > -1 && fy < (float)height:
+ *          no history
+ *        x0 = floor(fx), tx = fx - x0;  y0 = floor(fy), ty = fy - y0
+ *        taps j = 0, 1 outer, i = 0, 1 inner: q = prev's pixel at column x0 + i,
+ *        bottom row y0 + j (frame index (height - 1 - row) * width + column).
+ *        A tap is skipped when q is outside the image; when len_q > 0 is false;
+ *        when prim_q != prim_p; when
+ *          fabs(dot3(pos_q - P, normal_p)) <= sigma_z * t_p
+ *        is false; and when, with wx = i ? tx : 1 - tx, wy = j ? ty : 1 - ty,
+ *        w = wx * wy, w > 0 is false.  Else
+ *          cs_k = cs_k + w * c_q,k;  ls = ls + w * len_q;  ws = ws + w
+ *        ws > 0 false: no history.  Else hc_k = cs_k / ws, hl = ls / ws.
+ *      Blend.  No history: out_k = m_k, len = nf.  With history:
+ *        cap = max_history > nf ? max_history : nf
+ *        tl = hl + nf;  tl = tl > cap ? cap : tl;  alpha = nf / tl
+ *        out_k = hc_k + (m_k - hc_k) * alpha;  len = tl
+ *   6. cur becomes {out, len} with the guide of g, camera C, valid.  Resolving
+ *      again under the same camera recomputes cur from the same prev and the
+ *      accumulator's newer mean: the result is a function of (prev, accumulator
+ *      state), whatever the call pattern.
+ *   7. Outputs: the f32 out, its RGBA8 (sqrt(out_k) * 255.999 as u8, alpha 255,
+ *      as the frame resolve) or both.  With filter options the outputs are the
+ *      edge-aware filter above of out with the records g; the history always
+ *      stores the unfiltered out.  With prev invalid and no filter the RGBA8
+ *      output is the accumulator's last frame byte for byte.
+ *
+ * Known limits: reflections and refractions are reprojected with the surface
+ * that shows them, so they lag and ghost; sky takes no history; there is no
+ * variance clamp. */
+typedef struct RtHistoryOptions {
+  float max_history;   /* finite, >= 1; default 32: the length a pixel's history is capped at */
+  float sigma_z;       /* finite, > 0; default 0.02: the filter's plane-distance scale          */
+} RtHistoryOptions;
+
+/* max_history 32, sigma_z 0.02. */
+void rt_history_default_options(RtHistoryOptions *opts);
+/* Every call below returns 0 or a negative error with rt_last_error naming the
+ * call and the argument.  Checked before a device is looked for: a null
+ * accumulator, both outputs null, options out of range (the history's and the
+ * filter's), a history that is not enabled, an accumulator of 2^31 pixels or
+ * more.  Without a GPU every call that runs a kernel fails.
+ *
+ * Gives the accumulator a history with these options (NULL = the defaults), at
+ * any time; both snapshots are dropped.  Buffers are allocated by the first
+ * resolve and freed by rt_history_disable and rt_accum_free. */
+int rt_history_enable(RtAccum *acc, const RtHistoryOptions *opts);
+int rt_history_disable(RtAccum *acc);
+/* Drops both snapshots and keeps the setting. */
+int rt_history_reset(RtAccum *acc);
+/* Resolves (above) to host memory, synchronous: out_rgb width*height*3 f32 and
+ * / or pixels, top row first.  filter NULL: no filter. */
+int rt_history_resolve(RtAccum *acc, const RtFilterOptions *filter, float *out_rgb,
+                       Rust_ColorU8 *pixels);
+/* The same to DEVICE memory on hip_stream (NULL = the library's stream), only
+ * enqueued; ordered against passes, frames and filters as rt_filter_accum_device. */
+int rt_history_resolve_device(RtAccum *acc, const RtFilterOptions *filter, float *d_out_rgb,
+                              void *d_rgba, void *hip_stream);
+/* cur's length plane: width*height f32, top row first, all 0 when cur is
+ * invalid.  Waits for the last resolve. */
+int rt_history_read_length(RtAccum *acc, float *len);
+/* Step 5 alone on host arrays, synchronous, on `device` (-1 = current):
+ * prev_cam the 12 floats of prev's camera, prev_rgbl {r, g, b, len} and
+ * prev_records of prev (prev_rgbl NULL: prev is invalid; prev_cam and
+ * prev_records are then not read), rgb the means m (3 f32 per pixel), n the
+ * samples per pixel, records the current view's; out_rgbl {out, len}.  All
+ * arrays width*height entries, top row first. */
+int rt_history_run(size_t width, size_t height, const RtHistoryOptions *opts,
+                   const float *prev_cam, const float *prev_rgbl, const RtFirstHit *prev_records,
+                   const float *rgb, const uint32_t *n, const RtFirstHit *records, float *out_rgbl,
+                   int device);
+
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).
  * That launch must have been rendered with RT_FLAG_KEEP_SAMPLES.  Output

@@ -655,6 +655,93 @@ int rt_filter_accum_device(RtAccum *acc, const RtFilterOptions *opts, float *d_o
                                "rt_filter_accum_device");
 }
 
+// ---- temporal reprojection
+void rt_history_default_options(RtHistoryOptions *o) {
+    o->max_history = 32.0f;
+    o->sigma_z = 0.02f;
+}
+
+namespace {
+// the options (null: the defaults), checked; false with the error set
+bool history_options(const RtHistoryOptions *opts, const char *who, RtHistoryOptions &o) {
+    if (opts) o = *opts;
+    else rt_history_default_options(&o);
+    if (!(o.max_history >= 1.0f) || !(o.max_history <= 3.4028234663852886e38f)) {
+        rtamd::set_error(std::string(who) + ": max_history must be finite and >= 1");
+        return false;
+    }
+    if (!(o.sigma_z > 0.0f) || !(o.sigma_z <= 3.4028234663852886e38f)) {
+        rtamd::set_error(std::string(who) + ": sigma_z must be finite and > 0");
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+int rt_history_enable(RtAccum *acc, const RtHistoryOptions *opts) {
+    // (the options first: a caller's mistake shows whatever the accumulator's state)
+    RtHistoryOptions o;
+    if (!history_options(opts, "rt_history_enable", o)) return -1;
+    const AccumCall call(acc, "rt_history_enable");
+    if (!call) return -1;
+    return rtamd::history_enable(*acc->state, call.cam(), true, o.max_history, o.sigma_z);
+}
+
+int rt_history_disable(RtAccum *acc) {
+    const AccumCall call(acc, "rt_history_disable");
+    return call ? rtamd::history_enable(*acc->state, call.cam(), false, 0.0f, 0.0f) : -1;
+}
+
+int rt_history_reset(RtAccum *acc) {
+    const AccumCall call(acc, "rt_history_reset");
+    return call ? rtamd::history_reset(*acc->state, call.cam()) : -1;
+}
+
+int rt_history_resolve(RtAccum *acc, const RtFilterOptions *filter, float *out_rgb, Rust_ColorU8 *pixels) {
+    if (rtamd::history_check(filter, out_rgb, pixels, "rt_history_resolve")) return -1;
+    const AccumCall call(acc, "rt_history_resolve");
+    if (!call) return -1;
+    return rtamd::history_resolve(acc->state, &call.cam(), filter, out_rgb, pixels, false, nullptr,
+                                  "rt_history_resolve");
+}
+
+int rt_history_resolve_device(RtAccum *acc, const RtFilterOptions *filter, float *d_out_rgb, void *d_rgba,
+                              void *hip_stream) {
+    if (rtamd::history_check(filter, d_out_rgb, d_rgba, "rt_history_resolve_device")) return -1;
+    const AccumCall call(acc, "rt_history_resolve_device");
+    if (!call) return -1;
+    return rtamd::history_resolve(acc->state, &call.cam(), filter, d_out_rgb, d_rgba, true,
+                                  static_cast<hipStream_t>(hip_stream), "rt_history_resolve_device");
+}
+
+int rt_history_read_length(RtAccum *acc, float *len) {
+    const AccumCall call(acc, "rt_history_read_length");
+    return call ? rtamd::history_read_length(*acc->state, call.cam(), len) : -1;
+}
+
+int rt_history_run(size_t width, size_t height, const RtHistoryOptions *opts, const float *prev_cam,
+                   const float *prev_rgbl, const RtFirstHit *prev_records, const float *rgb, const uint32_t *n,
+                   const RtFirstHit *records, float *out_rgbl, int device) {
+    const char *who = "rt_history_run";
+    auto fail = [&](const char *msg) {
+        rtamd::set_error(std::string(who) + ": " + msg);
+        return -1;
+    };
+    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
+        (uint64_t)width * height >= (1ull << 31))
+        return fail("image size: width and height at least 1, width * height below 2^31");
+    RtHistoryOptions o;
+    if (!history_options(opts, who, o)) return -1;
+    if (prev_rgbl && !prev_cam) return fail("null input: prev_cam (with prev_rgbl given)");
+    if (prev_rgbl && !prev_records) return fail("null input: prev_records (with prev_rgbl given)");
+    if (!rgb) return fail("null input: rgb");
+    if (!n) return fail("null input: n");
+    if (!records) return fail("null input: records");
+    if (!out_rgbl) return fail("null output: out_rgbl");
+    return rtamd::history_run(width, height, o.max_history, o.sigma_z, prev_cam, prev_rgbl, prev_records, rgb, n,
+                              records, out_rgbl, device);
+}
+
 int rt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

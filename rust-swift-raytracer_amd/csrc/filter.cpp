@@ -27,7 +27,9 @@ int check_size(size_t width, size_t height, const char *who) {
     return 0;
 }
 
-int check_options(const RtFilterOptions *opts, const char *who, RtFilterOptions &o) {
+}  // namespace
+
+int filter_check_options(const RtFilterOptions *opts, const char *who, RtFilterOptions &o) {
     if (opts) o = *opts;
     else rt_filter_default_options(&o);
     if (o.levels < 0 || o.levels > 8) return fail(who, "levels must be 0 to 8");
@@ -38,15 +40,15 @@ int check_options(const RtFilterOptions *opts, const char *who, RtFilterOptions 
     return 0;
 }
 
-int check_outputs(const void *out_rgb, const void *out_rgba, const char *who) {
+int filter_check_outputs(const void *out_rgb, const void *out_rgba, const char *who) {
     if (!out_rgb && !out_rgba) return fail(who, "null output: give out_rgb, the RGBA8 output or both");
     return 0;
 }
 
 // The pack and the levels on s, ordered after the filter's last run.  src: the
 // input form (rgb, or sums / plane / count / held) and the records.
-int enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, float *d_out_rgb, uint32_t *d_out_rgba,
-            hipStream_t s) {
+int filter_enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, float *d_out_rgb, uint32_t *d_out_rgba,
+                   hipStream_t s) {
     const size_t npix = f.width * f.height;
     if (!f.done) HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
     HIP_TRY(f.col[0].grow(npix));
@@ -83,7 +85,7 @@ int enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, float *d_o
 }
 
 // Device staging of the host outputs asked for, and their copies back (waits).
-int stage_outputs(FilterState &f, float *out_rgb, void *out_rgba, float *&d_rgb, uint32_t *&d_rgba) {
+int filter_stage_outputs(FilterState &f, float *out_rgb, void *out_rgba, float *&d_rgb, uint32_t *&d_rgba) {
     const size_t npix = f.width * f.height;
     d_rgb = nullptr;
     d_rgba = nullptr;
@@ -98,7 +100,7 @@ int stage_outputs(FilterState &f, float *out_rgb, void *out_rgba, float *&d_rgb,
     return 0;
 }
 
-int fetch_outputs(FilterState &f, float *out_rgb, void *out_rgba, hipStream_t s) {
+int filter_fetch_outputs(FilterState &f, float *out_rgb, void *out_rgba, hipStream_t s) {
     const size_t npix = f.width * f.height;
     if (out_rgb)
         HIP_TRY(hipMemcpyAsync(out_rgb, f.out_rgb.get(), 3 * npix * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -106,8 +108,6 @@ int fetch_outputs(FilterState &f, float *out_rgb, void *out_rgba, hipStream_t s)
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
-
-}  // namespace
 
 FilterState::~FilterState() {
     if (device >= 0 && (done || stream) && hipSetDevice(device) == hipSuccess) {
@@ -132,10 +132,10 @@ int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, co
     if (!f) return fail(who, "null filter");
     if (!rgb) return fail(who, "null input: rgb");
     if (!records) return fail(who, "null input: records");
-    int rc = check_outputs(out_rgb, out_rgba, who);
+    int rc = filter_check_outputs(out_rgb, out_rgba, who);
     if (rc) return rc;
     RtFilterOptions o;
-    rc = check_options(opts, who, o);
+    rc = filter_check_options(opts, who, o);
     if (rc) return rc;
 
     std::lock_guard<std::mutex> lock(f->mu);
@@ -164,7 +164,7 @@ int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, co
     } else {
         HIP_TRY(f->in_rgb.grow(3 * npix));
         HIP_TRY(f->in_rec.grow(npix * (sizeof(RtFirstHit) / 4)));
-        rc = stage_outputs(*f, out_rgb, out_rgba, d_rgb, d_rgba);
+        rc = filter_stage_outputs(*f, out_rgb, out_rgba, d_rgb, d_rgba);
         if (rc) return rc;
         // (the staging may still be read by the last run, on another stream)
         if (f->done_stream && f->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f->done, 0));
@@ -173,19 +173,53 @@ int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, co
         src.rgb = f->in_rgb.get();
         src.records = reinterpret_cast<const float4 *>(f->in_rec.get());
     }
-    rc = enqueue(*f, o, src, d_rgb, d_rgba, s);
+    rc = filter_enqueue(*f, o, src, d_rgb, d_rgba, s);
     if (rc) return rc;
-    return on_device ? 0 : fetch_outputs(*f, out_rgb, out_rgba, s);
+    return on_device ? 0 : filter_fetch_outputs(*f, out_rgb, out_rgba, s);
+}
+
+FilterState &accum_filter(AccumState &a) {
+    if (!a.filter) {
+        a.filter = std::make_unique<FilterState>();
+        a.filter->width = a.width;
+        a.filter->height = a.height;
+        a.filter->device = a.device;
+    }
+    return *a.filter;
+}
+
+int accum_records(AccumState &a, WorldState &w, const CameraModel &cam, FilterState &f, hipStream_t s,
+                  const char *who) {
+    const size_t npix = a.width * a.height;
+    int rc = 0;
+    // the records of the camera and scene the held samples were traced with
+    // (a.cam is the handle's camera here: the reset rule has just been applied)
+    if (!a.rec_valid || std::memcmp(a.rec_cam, a.cam, sizeof(a.cam)) != 0 || a.rec_edit != a.edit_version) {
+        a.rec_valid = false;
+        HIP_TRY(a.records.grow(npix * (sizeof(RtFirstHit) / 4)));
+        // (the last run, on another stream, may still read the old ones)
+        if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
+        RtFirstHitOptions fo;
+        rt_first_hit_default_options(&fo);
+        fo.device = a.device;
+        fo.accel = a.accel;
+        rc = first_hit(w, cam, a.width, a.height, &fo, false, 0, a.records.get(), s, nullptr, who);
+        if (rc) return rc;
+        std::memcpy(a.rec_cam, a.cam, sizeof(a.cam));
+        a.rec_edit = a.edit_version;
+        a.rec_valid = true;
+    }
+    return 0;
 }
 
 int filter_accum(AccumState *ap, const CameraModel *cam, const RtFilterOptions *opts, float *out_rgb, void *out_rgba,
                  bool on_device, hipStream_t stream, const char *who) {
     if (!ap || !cam) return fail(who, "null accumulator");
     AccumState &a = *ap;
-    int rc = check_outputs(out_rgb, out_rgba, who);
+    int rc = filter_check_outputs(out_rgb, out_rgba, who);
     if (rc) return rc;
     RtFilterOptions o;
-    rc = check_options(opts, who, o);
+    rc = filter_check_options(opts, who, o);
     if (rc) return rc;
     if ((uint64_t)a.width * a.height >= (1ull << 31))
         return fail(who, "the accumulator's frame has 2^31 pixels or more: the filter takes width * height below "
@@ -201,13 +235,7 @@ int filter_accum(AccumState *ap, const CameraModel *cam, const RtFilterOptions *
     if (rc) return rc;
     hipStream_t s = stream ? stream : d->stream;
     const size_t npix = a.width * a.height;
-    if (!a.filter) {
-        a.filter = std::make_unique<FilterState>();
-        a.filter->width = a.width;
-        a.filter->height = a.height;
-        a.filter->device = a.device;
-    }
-    FilterState &f = *a.filter;
+    FilterState &f = accum_filter(a);
     std::lock_guard<std::mutex> flock(f.mu);
     // d->done is recorded again below, on s: it must still stand for the frame
     // another stream may be running, which the next frame on s has to wait for
@@ -215,23 +243,8 @@ int filter_accum(AccumState *ap, const CameraModel *cam, const RtFilterOptions *
     // after the accumulator's last pass, like its other readers
     if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
 
-    // the records of the camera and scene the held samples were traced with
-    // (a.cam is the handle's camera here: the reset rule has just been applied)
-    if (!a.rec_valid || std::memcmp(a.rec_cam, a.cam, sizeof(a.cam)) != 0 || a.rec_edit != a.edit_version) {
-        a.rec_valid = false;
-        HIP_TRY(a.records.grow(npix * (sizeof(RtFirstHit) / 4)));
-        // (the last run, on another stream, may still read the old ones)
-        if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
-        RtFirstHitOptions fo;
-        rt_first_hit_default_options(&fo);
-        fo.device = a.device;
-        fo.accel = a.accel;
-        rc = first_hit(w, *cam, a.width, a.height, &fo, false, 0, a.records.get(), s, nullptr, who);
-        if (rc) return rc;
-        std::memcpy(a.rec_cam, a.cam, sizeof(a.cam));
-        a.rec_edit = a.edit_version;
-        a.rec_valid = true;
-    }
+    rc = accum_records(a, w, *cam, f, s, who);
+    if (rc) return rc;
 
     FilterPack src{};
     src.sums = a.sums.get();
@@ -242,17 +255,17 @@ int filter_accum(AccumState *ap, const CameraModel *cam, const RtFilterOptions *
     float *d_rgb = out_rgb;
     uint32_t *d_rgba = static_cast<uint32_t *>(out_rgba);
     if (!on_device) {
-        rc = stage_outputs(f, out_rgb, out_rgba, d_rgb, d_rgba);
+        rc = filter_stage_outputs(f, out_rgb, out_rgba, d_rgb, d_rgba);
         if (rc) return rc;
     }
-    rc = enqueue(f, o, src, d_rgb, d_rgba, s);
+    rc = filter_enqueue(f, o, src, d_rgb, d_rgba, s);
     if (rc) return rc;
     // the next pass, on whatever stream, writes the sums after this run read them
     HIP_TRY(hipEventRecord(d->done, s));
     d->done_stream = s;
     HIP_TRY(hipEventRecord(a.done, s));
     a.done_stream = s;
-    return on_device ? 0 : fetch_outputs(f, out_rgb, out_rgba, s);
+    return on_device ? 0 : filter_fetch_outputs(f, out_rgb, out_rgba, s);
 }
 
 }  // namespace rtamd

@@ -1,0 +1,262 @@
+// history.cpp -- temporal reprojection, host side (rt_history_*).
+//
+// Keeps an accumulator's two snapshots (which one is cur, what camera and scene
+// version each was made under), computes prev's camera constants and enqueues
+// history.hip's resolve kernel in front of the outputs or of the edge-aware
+// filter.  Ordered on the stream exactly as filter_accum, whose records cache,
+// filter state and output staging it shares (runtime_internal.h).
+#include <algorithm>
+
+#include "runtime_internal.h"
+
+namespace rtamd {
+
+namespace {
+
+int fail(const char *who, const std::string &msg) {
+    set_error(std::string(who) + ": " + msg);
+    return -1;
+}
+
+// a x b as maths.rs:88-94: each product rounded, then the subtraction
+void cross(const float a[3], const float b[3], float out[3]) {
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = -(a[0] * b[2] - a[2] * b[0]);
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// prev's camera constants (this unit compiles without contraction: one rounded
+// operation per step, the bits a lane would compute)
+void history_camera(const float cam[12], HistoryResolve &k) {
+    const float *O = cam, *L = cam + 3, *H = cam + 6, *V = cam + 9;
+    const float A[3] = {L[0] - O[0], L[1] - O[1], L[2] - O[2]};
+    cross(H, V, k.n0);
+    cross(V, A, k.n1);
+    cross(A, H, k.n2);
+    k.det = ((A[0] * k.n0[0]) + (A[1] * k.n0[1])) + (A[2] * k.n0[2]);
+    for (int i = 0; i < 3; ++i) k.org[i] = O[i];
+}
+
+void drop_snapshots(AccumState &a) {
+    a.hist[0].valid = false;
+    a.hist[1].valid = false;
+}
+
+}  // namespace
+
+int history_check(const RtFilterOptions *filter, const void *out_rgb, const void *out_rgba, const char *who) {
+    int rc = filter_check_outputs(out_rgb, out_rgba, who);
+    if (rc) return rc;
+    RtFilterOptions o;
+    return filter ? filter_check_options(filter, who, o) : 0;
+}
+
+int history_enable(AccumState &a, const CameraModel &cam, bool on, float max_history, float sigma_z) {
+    // (the options were checked by rt_history_enable, before the accumulator)
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!accum_begin(a, cam, lock)) return -1;
+    drop_snapshots(a);
+    a.hist_enabled = on;
+    if (on) {
+        a.hist_max = max_history;
+        a.hist_sigma_z = sigma_z;
+        return 0;
+    }
+    // (the last resolve may still use the buffers)
+    if (a.device >= 0 && a.done_stream) {
+        HIP_TRY(hipSetDevice(a.device));
+        HIP_TRY(hipEventSynchronize(a.done));
+    }
+    for (auto &h : a.hist) {
+        h.col.reset();
+        h.guide.reset();
+    }
+    a.hist_rgb.reset();
+    return 0;
+}
+
+int history_reset(AccumState &a, const CameraModel &cam) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!accum_begin(a, cam, lock)) return -1;
+    if (!a.hist_enabled) return fail("rt_history_reset", "the accumulator's history is not enabled");
+    drop_snapshots(a);
+    return 0;
+}
+
+int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOptions *filter, float *out_rgb,
+                    void *out_rgba, bool on_device, hipStream_t stream, const char *who) {
+    if (!ap || !cam) return fail(who, "null accumulator");
+    AccumState &a = *ap;
+    // (the entry point has been through history_check already: a caller's mistake
+    // shows whatever the accumulator's state)
+    int rc = history_check(filter, out_rgb, out_rgba, who);
+    if (rc) return rc;
+    RtFilterOptions fo{};
+    if (filter) fo = *filter;
+    if ((uint64_t)a.width * a.height >= (1ull << 31))
+        return fail(who, "the accumulator's frame has 2^31 pixels or more: a history takes width * height below "
+                         "2^31 (an accumulator up to 2^32 - 1)");
+
+    std::unique_lock<std::recursive_mutex> lock;
+    WorldState *wp = accum_begin(a, *cam, lock);
+    if (!wp) return fail(who, "the accumulator's world was freed");
+    WorldState &w = *wp;
+    if (!a.hist_enabled) return fail(who, "the accumulator's history is not enabled (rt_history_enable)");
+    if (a.held == 0) return fail(who, "no samples held");
+    DeviceState *d = nullptr;
+    rc = device_for(w, a.device, d);
+    if (rc) return rc;
+    hipStream_t s = stream ? stream : d->stream;
+    const size_t npix = a.width * a.height;
+    FilterState &f = accum_filter(a);
+    std::lock_guard<std::mutex> flock(f.mu);
+    for (auto &h : a.hist) {
+        HIP_TRY(h.col.grow(npix));
+        HIP_TRY(h.guide.grow(npix));
+    }
+    if (filter) HIP_TRY(a.hist_rgb.grow(3 * npix));
+    if (!f.done) HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+    // as filter_accum: d->done is recorded again below, on s ...
+    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
+    // ... after the accumulator's last pass and its last resolve (the snapshots) ...
+    if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
+    // ... and after the filter's last run (its staging is written below)
+    if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
+
+    // a snapshot of another scene: both go; a cur of another camera becomes prev
+    for (const auto &h : a.hist)
+        if (h.valid && h.edit != a.edit_version) drop_snapshots(a);
+    if (a.hist[a.hist_cur].valid && std::memcmp(a.hist[a.hist_cur].cam, a.cam, sizeof(a.cam)) != 0) a.hist_cur ^= 1u;
+    AccumState::HistorySnap &cur = a.hist[a.hist_cur], &prev = a.hist[a.hist_cur ^ 1u];
+    // (valid again once the kernel that fills it is enqueued)
+    cur.valid = false;
+
+    rc = accum_records(a, w, *cam, f, s, who);
+    if (rc) return rc;
+
+    float *d_rgb = out_rgb;
+    uint32_t *d_rgba = static_cast<uint32_t *>(out_rgba);
+    if (!on_device) {
+        rc = filter_stage_outputs(f, out_rgb, out_rgba, d_rgb, d_rgba);
+        if (rc) return rc;
+    }
+    HistoryResolve k{};
+    k.sums = a.sums.get();
+    k.plane = npix;
+    k.count = a.adaptive ? a.count.get() : nullptr;
+    k.held = a.held;
+    k.records = reinterpret_cast<const float4 *>(a.records.get());
+    if (prev.valid) {
+        k.prev_col = prev.col.get();
+        k.prev_guide = prev.guide.get();
+        history_camera(prev.cam, k);
+    }
+    k.max_history = a.hist_max;
+    k.sigma_z = a.hist_sigma_z;
+    k.cur_col = cur.col.get();
+    k.cur_guide = cur.guide.get();
+    k.out_rgb = filter ? a.hist_rgb.get() : d_rgb;
+    k.out_rgba = filter ? nullptr : d_rgba;
+    k.width = (uint32_t)a.width;
+    k.height = (uint32_t)a.height;
+    HIP_TRY(launch_history_resolve(k, s));
+    std::memcpy(cur.cam, a.cam, sizeof(a.cam));
+    cur.edit = a.edit_version;
+    cur.valid = true;
+    if (filter) {
+        // the filter of the blended image with the same records; the history keeps the unfiltered one
+        FilterPack src{};
+        src.rgb = a.hist_rgb.get();
+        src.records = k.records;
+        rc = filter_enqueue(f, fo, src, d_rgb, d_rgba, s);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(hipEventRecord(f.done, s));
+        f.done_stream = s;
+    }
+    // the next pass, on whatever stream, writes the sums after this run read them
+    HIP_TRY(hipEventRecord(d->done, s));
+    d->done_stream = s;
+    HIP_TRY(hipEventRecord(a.done, s));
+    a.done_stream = s;
+    return on_device ? 0 : filter_fetch_outputs(f, out_rgb, out_rgba, s);
+}
+
+int history_read_length(AccumState &a, const CameraModel &cam, float *len) {
+    if (!len) return fail("rt_history_read_length", "null output: len");
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!accum_begin(a, cam, lock)) return -1;
+    if (!a.hist_enabled) return fail("rt_history_read_length", "the accumulator's history is not enabled");
+    const size_t npix = a.width * a.height;
+    const AccumState::HistorySnap &cur = a.hist[a.hist_cur];
+    if (!cur.valid) {
+        std::fill(len, len + npix, 0.0f);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(a.device));
+    HIP_TRY(hipEventSynchronize(a.done));
+    std::vector<float4> col(npix);
+    HIP_TRY(hipMemcpy(col.data(), cur.col.get(), npix * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; ++i) len[i] = col[i].w;
+    return 0;
+}
+
+int history_run(size_t width, size_t height, float max_history, float sigma_z, const float *prev_cam,
+                const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
+                const void *records, float *out_rgbl, int device) {
+    // (the arguments were checked by rt_history_run)
+    const char *who = "rt_history_run";
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        set_error(std::string(who) + ": no HIP device available: the MI355X render path requires a GPU");
+        return -3;
+    }
+    int dev = device;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    if (dev >= count) return fail(who, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(dev));
+    const size_t npix = width * height;
+    DevBuf<float> d_rgb;
+    DevBuf<uint32_t> d_n, d_rec;
+    DevBuf<float4> d_prev_col, d_prev_guide, d_out;
+    HIP_TRY(d_rgb.grow(3 * npix));
+    HIP_TRY(d_n.grow(npix));
+    HIP_TRY(d_rec.grow(npix * (sizeof(RtFirstHit) / 4)));
+    HIP_TRY(d_out.grow(npix));
+    HIP_TRY(hipMemcpy(d_rgb.get(), rgb, 3 * npix * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_n.get(), n, npix * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_rec.get(), records, npix * sizeof(RtFirstHit), hipMemcpyHostToDevice));
+    HistoryResolve k{};
+    if (prev_rgbl) {
+        // a snapshot's guide: {position, prim bits} of its records
+        const RtFirstHit *pr = static_cast<const RtFirstHit *>(prev_records);
+        std::vector<float4> guide(npix);
+        for (size_t i = 0; i < npix; ++i) {
+            guide[i].x = pr[i].position[0];
+            guide[i].y = pr[i].position[1];
+            guide[i].z = pr[i].position[2];
+            std::memcpy(&guide[i].w, &pr[i].prim, sizeof(float));
+        }
+        HIP_TRY(d_prev_col.grow(npix));
+        HIP_TRY(d_prev_guide.grow(npix));
+        HIP_TRY(hipMemcpy(d_prev_col.get(), prev_rgbl, npix * sizeof(float4), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_prev_guide.get(), guide.data(), npix * sizeof(float4), hipMemcpyHostToDevice));
+        k.prev_col = d_prev_col.get();
+        k.prev_guide = d_prev_guide.get();
+        history_camera(prev_cam, k);
+    }
+    k.rgb = d_rgb.get();
+    k.n = d_n.get();
+    k.records = reinterpret_cast<const float4 *>(d_rec.get());
+    k.max_history = max_history;
+    k.sigma_z = sigma_z;
+    k.cur_col = d_out.get();
+    k.width = (uint32_t)width;
+    k.height = (uint32_t)height;
+    // (the null stream: the copies above are done, the one below follows the kernel)
+    HIP_TRY(launch_history_resolve(k, nullptr));
+    HIP_TRY(hipMemcpy(out_rgbl, d_out.get(), npix * sizeof(float4), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // namespace rtamd

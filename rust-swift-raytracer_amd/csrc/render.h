@@ -395,6 +395,33 @@ struct FilterLevel {
     uint32_t same_prim;
 };
 hipError_t launch_filter_level(const FilterLevel &a, hipStream_t stream);
+// Temporal reprojection (history.hip; DESIGN.md 5.10, include/raytracer_amd.h
+// rt_history_*): step 5 of a resolve.  One lane per pixel, a wave per 8 x 8
+// tile, finds its record's position in prev's view, gathers up to 4 taps of
+// prev_col {r, g, b, len} and prev_guide {position, prim bits}, blends them
+// with the pixel's mean and writes cur_col, cur_guide (may be null) and the
+// outputs (each may be null).  The mean is rgb[3 i + k] with n[i] samples
+// (rt_history_run), or, with rgb null, sums[k * plane + i] * inv with
+// inv = 1.0f / (float)n and n = count[i] where count is given, else held.
+// prev_col null: prev is invalid.  org, n0, n1, n2, det: prev's camera
+// constants (history.cpp history_camera), the same for every lane.
+struct HistoryResolve {
+    const float *rgb;
+    const uint32_t *n;
+    const float *sums;
+    size_t plane;
+    const uint32_t *count;
+    uint32_t held;
+    const float4 *records;
+    const float4 *prev_col, *prev_guide;
+    float org[3], n0[3], n1[3], n2[3], det;
+    float max_history, sigma_z;
+    float4 *cur_col, *cur_guide;
+    float *out_rgb;
+    uint32_t *out_rgba;
+    uint32_t width, height;
+};
+hipError_t launch_history_resolve(const HistoryResolve &a, hipStream_t stream);
 // The adaptive accumulator's list kernels (adapt.hip).  iota: list[i] = i.
 // select: one thread per entry i < n of list: count[list[i]] = N and, with
 // decide, keep[i] = 0 iff the pixel converged by the rule of DESIGN.md 5.7

@@ -305,6 +305,23 @@ struct AccumState {
     float rec_cam[12] = {};
     uint64_t rec_edit = 0;
     bool rec_valid = false;
+    // The history of resolved views (rt_history_*): two
+    // snapshots, hist[hist_cur] the last resolve's and the other one prev, each
+    // valid for the camera and scene version it was made under.  Allocated by
+    // the first resolve; hist_rgb is the blended image a filtered resolve hands
+    // to the filter.
+    struct HistorySnap {
+        DevBuf<float4> col;       // {r, g, b, len}
+        DevBuf<float4> guide;     // {position, prim bits}
+        float cam[12] = {};
+        uint64_t edit = 0;
+        bool valid = false;
+    };
+    bool hist_enabled = false;
+    float hist_max = 0.0f, hist_sigma_z = 0.0f;
+    HistorySnap hist[2];
+    uint32_t hist_cur = 0;
+    DevBuf<float> hist_rgb;
 };
 
 // One pass of an accumulation, for render_frame: n0 samples held, the frame's
@@ -414,6 +431,20 @@ int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, co
                void *out_rgba, bool on_device, hipStream_t stream, const char *who);
 int filter_accum(AccumState *a, const CameraModel *cam, const RtFilterOptions *opts, float *out_rgb, void *out_rgba,
                  bool on_device, hipStream_t stream, const char *who);
+// Temporal reprojection (rt_history_*, include/raytracer_amd.h).
+// check: a resolve's arguments that need no accumulator (outputs, the filter's
+// options when given), with a message.  enable (on false: disable, which also
+// frees the buffers) and reset drop both snapshots.  resolve: as filter_accum, with the history's
+// step in front; filter null: no filter.  run: step 5 on host arrays.
+int history_check(const RtFilterOptions *filter, const void *out_rgb, const void *out_rgba, const char *who);
+int history_enable(AccumState &a, const CameraModel &cam, bool on, float max_history, float sigma_z);
+int history_reset(AccumState &a, const CameraModel &cam);
+int history_resolve(AccumState *a, const CameraModel *cam, const RtFilterOptions *filter, float *out_rgb,
+                    void *out_rgba, bool on_device, hipStream_t stream, const char *who);
+int history_read_length(AccumState &a, const CameraModel &cam, float *len);
+int history_run(size_t width, size_t height, float max_history, float sigma_z, const float *prev_cam,
+                const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
+                const void *records, float *out_rgbl, int device);
 // Waits for device d's pending counted frame and fills stats from it.
 int collect_frame_stats(DeviceState *d, RtRenderStats *stats);
 

@@ -86,6 +86,24 @@ int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size
 // camera or an edited scene drops the held samples); nullptr with the error set
 WorldState *accum_begin(AccumState &a, const CameraModel &cam, std::unique_lock<std::recursive_mutex> &lock);
 
+// filter.cpp, for history.cpp: a filter call's checks (who: the entry point, for
+// the messages; o: the options checked, the defaults for null) ...
+int filter_check_outputs(const void *out_rgb, const void *out_rgba, const char *who);
+int filter_check_options(const RtFilterOptions *opts, const char *who, RtFilterOptions &o);
+// ... the accumulator's filter state, created on first use ...
+FilterState &accum_filter(AccumState &a);
+// ... the accumulator's first-hit records made current on s: those of the camera
+// and scene version its held samples were traced with, kept until either changes
+// (cam: the handle's camera, a.cam's after the reset rule) ...
+int accum_records(AccumState &a, WorldState &w, const CameraModel &cam, FilterState &f, hipStream_t s, const char *who);
+// ... the pack and the levels on s, ordered after the filter's last run (src:
+// the input form and the records) ...
+int filter_enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, float *d_out_rgb, uint32_t *d_out_rgba,
+                   hipStream_t s);
+// ... and device staging of the host outputs asked for, with their copies back (waits)
+int filter_stage_outputs(FilterState &f, float *out_rgb, void *out_rgba, float *&d_rgb, uint32_t *&d_rgba);
+int filter_fetch_outputs(FilterState &f, float *out_rgb, void *out_rgba, hipStream_t s);
+
 // multi.cpp: devices [first, first + n) (first < 0: from the current device), checked
 int device_list(int first, int n, std::vector<int> &devs);
 

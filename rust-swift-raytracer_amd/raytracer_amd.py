@@ -45,6 +45,8 @@ EXPORTS = (
     "rt_first_hit_view", "rt_first_hit_view_device",
     "rt_filter_default_options", "rt_filter_create", "rt_filter_free", "rt_filter_run_device",
     "rt_filter_run", "rt_filter_accum", "rt_filter_accum_device",
+    "rt_history_default_options", "rt_history_enable", "rt_history_disable", "rt_history_reset",
+    "rt_history_resolve", "rt_history_resolve_device", "rt_history_read_length", "rt_history_run",
 )
 
 
@@ -102,6 +104,11 @@ class FilterOptions(C.Structure):
     """raytracer_amd.h RtFilterOptions (defaults: 3, 0.5, 0.02, 5, 0)."""
     _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
                 ("normal_squarings", C.c_int32), ("flags", C.c_uint32)]
+
+
+class HistoryOptions(C.Structure):
+    """raytracer_amd.h RtHistoryOptions (defaults: 32, 0.02)."""
+    _fields_ = [("max_history", C.c_float), ("sigma_z", C.c_float)]
 
 
 class RenderStats(C.Structure):
@@ -290,6 +297,25 @@ def lib(path=None):
             L.rt_filter_accum.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p]
             L.rt_filter_accum_device.restype = C.c_int
             L.rt_filter_accum_device.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_history_enable"):  # (likewise)
+            LO = C.POINTER(FilterOptions)
+            HO = C.POINTER(HistoryOptions)
+            L.rt_history_default_options.restype = None
+            L.rt_history_default_options.argtypes = [HO]
+            L.rt_history_enable.restype = C.c_int
+            L.rt_history_enable.argtypes = [C.c_void_p, HO]
+            L.rt_history_disable.restype = C.c_int
+            L.rt_history_disable.argtypes = [C.c_void_p]
+            L.rt_history_reset.restype = C.c_int
+            L.rt_history_reset.argtypes = [C.c_void_p]
+            L.rt_history_resolve.restype = C.c_int
+            L.rt_history_resolve.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p]
+            L.rt_history_resolve_device.restype = C.c_int
+            L.rt_history_resolve_device.argtypes = [C.c_void_p, LO, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rt_history_read_length.restype = C.c_int
+            L.rt_history_read_length.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_history_run.restype = C.c_int
+            L.rt_history_run.argtypes = [C.c_size_t, C.c_size_t, HO] + [C.c_void_p] * 7 + [C.c_int]
         _libs[path] = L
     return _libs[path]
 
@@ -756,6 +782,45 @@ class Accumulator:
                                                    C.c_void_p(out_rgba_ptr or None),
                                                    C.c_void_p(stream_ptr or None)), "rt_filter_accum_device")
 
+    # ---- the resolved view carried across camera moves (rt_history_*)
+    def history_enable(self, **opts):
+        """rt_history_enable with the defaults overridden (max_history, sigma_z); drops both snapshots."""
+        o = history_options(self._L, **opts)
+        self._check(self._L.rt_history_enable(self._a, C.byref(o)), "rt_history_enable")
+
+    def history_disable(self):
+        self._check(self._L.rt_history_disable(self._a), "rt_history_disable")
+
+    def history_reset(self):
+        """Drops both snapshots and keeps the setting."""
+        self._check(self._L.rt_history_reset(self._a), "rt_history_reset")
+
+    def resolved(self, filter=None):
+        """rt_history_resolve -> (rgb float32[height, width, 3], rgba uint8[height, width, 4]): the
+        held samples blended with the history reprojected from the last camera.  filter: None,
+        or a dict of filter_options fields ({} = the default filter) applied to the result."""
+        o = None if filter is None else filter_options(self._L, **filter)
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        px = np.zeros((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rt_history_resolve(self._a, C.byref(o) if o is not None else None, out.ctypes.data,
+                                               px.ctypes.data), "rt_history_resolve")
+        return out, px
+
+    def resolved_device(self, out_rgb_ptr: int = 0, out_rgba_ptr: int = 0, stream_ptr: int = 0, filter=None):
+        """rt_history_resolve_device: into device memory, only enqueued on the stream."""
+        o = None if filter is None else filter_options(self._L, **filter)
+        self._check(self._L.rt_history_resolve_device(self._a, C.byref(o) if o is not None else None,
+                                                      C.c_void_p(out_rgb_ptr or None),
+                                                      C.c_void_p(out_rgba_ptr or None),
+                                                      C.c_void_p(stream_ptr or None)), "rt_history_resolve_device")
+
+    def history_length(self):
+        """The samples each pixel of the last resolve stands for: float32[height, width], top row
+        first (all 0 before the first resolve)."""
+        out = np.zeros((self.height, self.width), np.float32)
+        self._check(self._L.rt_history_read_length(self._a, out.ctypes.data), "rt_history_read_length")
+        return out
+
     def active_list(self):
         """The active list: uint32 frame indices (row * width + col, top row first), ascending."""
         out = np.zeros(self.width * self.height, np.uint32)
@@ -776,6 +841,48 @@ def filter_options(L=None, **opts):
             raise TypeError(f"unknown filter option {k!r}")
         setattr(o, k, (o.flags | v) if k == "flags" else v)
     return o
+
+
+def history_options(L=None, **opts):
+    """rt_history_default_options with the fields given overridden (max_history, sigma_z)."""
+    o = HistoryOptions()
+    (L or lib()).rt_history_default_options(C.byref(o))
+    for k, v in opts.items():
+        if k not in ("max_history", "sigma_z"):
+            raise TypeError(f"unknown history option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def history_run(rgb, n, records, prev_cam=None, prev_rgbl=None, prev_records=None, device=-1, L=None, **opts):
+    """rt_history_run: the reprojection and blend of one resolve on host arrays.  rgb
+    float32[height, width, 3] (the means), n uint32[height, width], records
+    FIRST_HIT_DTYPE[height, width]; prev_cam (12 floats), prev_rgbl float32[height, width, 4]
+    and prev_records of the last view, or all None for none -> float32[height, width, 4]
+    {r, g, b, len}."""
+    L = L or lib()
+    o = history_options(L, **opts)
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("rgb is height x width x 3 floats")
+    h, w = c.shape[:2]
+    cnt = np.ascontiguousarray(n, dtype=np.uint32)
+    g = np.ascontiguousarray(records, dtype=FIRST_HIT_DTYPE)
+    if cnt.size != w * h or g.size != w * h:
+        raise ValueError("n and records are height x width")
+    pc = pl = pg = None
+    if prev_rgbl is not None:
+        pc = np.ascontiguousarray(prev_cam, dtype=np.float32)
+        pl = np.ascontiguousarray(prev_rgbl, dtype=np.float32)
+        pg = np.ascontiguousarray(prev_records, dtype=FIRST_HIT_DTYPE)
+        if pc.size != 12 or pl.size != 4 * w * h or pg.size != w * h:
+            raise ValueError("prev_cam is 12 floats, prev_rgbl height x width x 4, prev_records height x width")
+    out = np.zeros((h, w, 4), np.float32)
+    rc = L.rt_history_run(w, h, C.byref(o), *(a.ctypes.data if a is not None else None for a in (pc, pl, pg)),
+                          c.ctypes.data, cnt.ctypes.data, g.ctypes.data, out.ctypes.data, device)
+    if rc != 0:
+        raise RenderError(f"rt_history_run failed ({rc}): {L.rt_last_error().decode()}")
+    return out
 
 
 class Filter:
