@@ -569,8 +569,8 @@ int rt_filter_accum_device(RtAccum *acc, const RtFilterOptions *opts, float *d_o
  *      output is the accumulator's last frame byte for byte.
  *
  * Known limits: reflections and refractions are reprojected with the surface
- * that shows them, so they lag and ghost; sky takes no history; there is no
- * variance clamp. */
+ * that shows them, so they lag and ghost unless the neighbourhood clamp below
+ * (rt_clamp_*) is enabled; sky takes no history. */
 typedef struct RtHistoryOptions {
   float max_history;   /* finite, >= 1; default 32: the length a pixel's history is capped at */
   float sigma_z;       /* finite, > 0; default 0.02: the filter's plane-distance scale          */
@@ -612,6 +612,85 @@ int rt_history_run(size_t width, size_t height, const RtHistoryOptions *opts,
                    const float *prev_cam, const float *prev_rgbl, const RtFirstHit *prev_records,
                    const float *rgb, const uint32_t *n, const RtFirstHit *records, float *out_rgbl,
                    int device);
+
+/* ---- Neighbourhood clamp of the reprojected history.
+ *
+ * A setting of the accumulator that rt_history_resolve and
+ * rt_history_resolve_device honour.  Disabled (the default), every call
+ * returns exactly what it returned without it.  Enabled, the history colour
+ * of a pixel is clamped, before the blend, to a box around the mean of the
+ * new samples of the pixel's neighbourhood, gamma standard deviations wide: a
+ * history that no longer agrees with what the new samples show (a reflection
+ * that moved, a material that was edited) is pulled to them instead of
+ * ghosting for max_history samples.
+ *
+ * The rules of the resolve hold: every step is one rounded f32 operation,
+ * unfused; / and sqrt are correctly rounded; comparisons are false for NaN;
+ * only + - * /, fabs, floor, sqrt and compares appear.
+ *
+ * The clamp is a step inside step 5 above, between hc_k = cs_k / ws and the
+ * blend, for pixels with history (ws > 0) only.  With r = radius, visit the
+ * taps q = p + (i - r, j - r) in frame coordinates (columns, rows from the
+ * top), j = 0 .. 2r outer, i = 0 .. 2r inner.  A q outside the image is
+ * skipped.  With c = 0 (an integer) and s1_k = s2_k = 0 before the first tap,
+ * each remaining tap:
+ *     m_q,k = sum_q,k * inv_q,  inv_q = 1.0f / (float)n_q
+ *       (the means of step 5: n_q the samples held, or count[q] on an adaptive
+ *        accumulator; rt_clamp_run's rgb are these means)
+ *     c = c + 1
+ *     s1_k = s1_k + m_q,k
+ *     s2_k = s2_k + (m_q,k * m_q,k)        (the product rounded, then the add)
+ * then
+ *     ic = 1.0f / (float)c
+ *     mu_k  = s1_k * ic
+ *     var_k = s2_k * ic - mu_k * mu_k      (both products rounded, then the subtraction)
+ *     var_k = var_k < 0 ? 0 : var_k        (NaN stays NaN)
+ *     wd_k  = gamma * sqrt(var_k);  lo_k = mu_k - wd_k;  hi_k = mu_k + wd_k
+ *     hc_k  = hc_k < lo_k ? lo_k : hc_k;  then  hc_k = hc_k > hi_k ? hi_k : hc_k
+ * A NaN bound leaves hc alone and a NaN hc stays NaN.  hl, tl, alpha, len and
+ * the blend are those of step 5, applied to the clamped hc; the history stores
+ * the blended out; a filter behind the resolve filters that out.  Pixels
+ * without history and sky pixels are untouched.  At 1 x 1 the box collapses
+ * onto the pixel's own mean: a pixel with history returns its mean on bits,
+ * with len = tl.
+ *
+ * RT_CLAMP_KEEP_ON_EDIT (only while the clamp is enabled with it): step 2 no
+ * longer invalidates snapshots made under another scene edit version, and
+ * step 3 swaps cur and prev when cur is valid and its camera or its edit
+ * version differs from the accumulator's.  The guides stay true because no
+ * edit moves a primitive (rt_world_set_*_material is all there is); the stale
+ * colours are what the clamp is for.  Without the flag, or with the clamp
+ * disabled, an edit drops both snapshots as before. */
+enum { RT_CLAMP_KEEP_ON_EDIT = 1 };  /* flags: a material edit keeps the history */
+
+typedef struct RtClampOptions {
+  float gamma;      /* finite, >= 0; default 1.5: half-width of the box in standard deviations */
+  int32_t radius;   /* 1 .. 3; default 1: the neighbourhood is (2*radius+1)^2 pixels           */
+  uint32_t flags;   /* RT_CLAMP_*; default 0; unknown bits are an error                         */
+} RtClampOptions;
+
+/* gamma 1.5, radius 1, flags 0. */
+void rt_clamp_default_options(RtClampOptions *opts);
+/* Every call below returns 0 or a negative error with rt_last_error naming the
+ * call and the argument; the options are checked first, then the accumulator,
+ * all before a device is looked for.
+ *
+ * Turns the clamp on with these options (NULL = the defaults), at any time,
+ * with or without an enabled history.  No snapshot is dropped: a resolve is a
+ * function of prev, the accumulator's state and the options.  The setting
+ * survives rt_history_enable, rt_history_disable and rt_history_reset and goes
+ * with rt_accum_free. */
+int rt_clamp_enable(RtAccum *acc, const RtClampOptions *opts);
+int rt_clamp_disable(RtAccum *acc);
+/* rt_history_run with the clamp (clamp NULL = the defaults): step 5 with the
+ * step above on host arrays.  out_box may be NULL; otherwise it receives
+ * {lo_r, lo_g, lo_b, hi_r, hi_g, hi_b} (6 f32) for EVERY pixel, with history
+ * or not, top row first: a mistake in the moments shows there, one in the
+ * blend in out_rgbl. */
+int rt_clamp_run(size_t width, size_t height, const RtHistoryOptions *opts,
+                 const RtClampOptions *clamp, const float *prev_cam, const float *prev_rgbl,
+                 const RtFirstHit *prev_records, const float *rgb, const uint32_t *n,
+                 const RtFirstHit *records, float *out_rgbl, float *out_box, int device);
 
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).

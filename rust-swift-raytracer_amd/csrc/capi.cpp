@@ -742,6 +742,73 @@ int rt_history_run(size_t width, size_t height, const RtHistoryOptions *opts, co
                               records, out_rgbl, device);
 }
 
+// ---- the resolve's neighbourhood clamp
+void rt_clamp_default_options(RtClampOptions *o) {
+    o->gamma = 1.5f;
+    o->radius = 1;
+    o->flags = 0;
+}
+
+namespace {
+// the options (null: the defaults), checked; false with the error set
+bool clamp_options(const RtClampOptions *opts, const char *who, RtClampOptions &o) {
+    if (opts) o = *opts;
+    else rt_clamp_default_options(&o);
+    if (!(o.gamma >= 0.0f) || !(o.gamma <= 3.4028234663852886e38f)) {
+        rtamd::set_error(std::string(who) + ": gamma must be finite and >= 0");
+        return false;
+    }
+    if (o.radius < 1 || o.radius > 3) {
+        rtamd::set_error(std::string(who) + ": radius must be 1 .. 3");
+        return false;
+    }
+    if (o.flags & ~(uint32_t)RT_CLAMP_KEEP_ON_EDIT) {
+        rtamd::set_error(std::string(who) + ": flags: unknown bits");
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+int rt_clamp_enable(RtAccum *acc, const RtClampOptions *opts) {
+    // (the options first, as rt_history_enable)
+    RtClampOptions o;
+    if (!clamp_options(opts, "rt_clamp_enable", o)) return -1;
+    const AccumCall call(acc, "rt_clamp_enable");
+    if (!call) return -1;
+    return rtamd::clamp_enable(*acc->state, call.cam(), true, o);
+}
+
+int rt_clamp_disable(RtAccum *acc) {
+    const AccumCall call(acc, "rt_clamp_disable");
+    return call ? rtamd::clamp_enable(*acc->state, call.cam(), false, RtClampOptions{}) : -1;
+}
+
+int rt_clamp_run(size_t width, size_t height, const RtHistoryOptions *opts, const RtClampOptions *clamp,
+                 const float *prev_cam, const float *prev_rgbl, const RtFirstHit *prev_records, const float *rgb,
+                 const uint32_t *n, const RtFirstHit *records, float *out_rgbl, float *out_box, int device) {
+    const char *who = "rt_clamp_run";
+    auto fail = [&](const char *msg) {
+        rtamd::set_error(std::string(who) + ": " + msg);
+        return -1;
+    };
+    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
+        (uint64_t)width * height >= (1ull << 31))
+        return fail("image size: width and height at least 1, width * height below 2^31");
+    RtHistoryOptions o;
+    if (!history_options(opts, who, o)) return -1;
+    RtClampOptions c;
+    if (!clamp_options(clamp, who, c)) return -1;
+    if (prev_rgbl && !prev_cam) return fail("null input: prev_cam (with prev_rgbl given)");
+    if (prev_rgbl && !prev_records) return fail("null input: prev_records (with prev_rgbl given)");
+    if (!rgb) return fail("null input: rgb");
+    if (!n) return fail("null input: n");
+    if (!records) return fail("null input: records");
+    if (!out_rgbl) return fail("null output: out_rgbl");
+    return rtamd::history_run(width, height, o.max_history, o.sigma_z, prev_cam, prev_rgbl, prev_records, rgb, n,
+                              records, out_rgbl, device, &c, out_box);
+}
+
 int rt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

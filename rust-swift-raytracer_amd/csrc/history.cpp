@@ -4,7 +4,10 @@
 // version each was made under), computes prev's camera constants and enqueues
 // history.hip's resolve kernel in front of the outputs or of the edge-aware
 // filter.  Ordered on the stream exactly as filter_accum, whose records cache,
-// filter state and output staging it shares (runtime_internal.h).
+// filter state and output staging it shares (runtime_internal.h).  The resolve's
+// neighbourhood clamp (rt_clamp_*) is a setting kept beside the
+// history's: it picks the kernel's clamped instance and, with
+// RT_CLAMP_KEEP_ON_EDIT, lets the snapshots outlive a material edit.
 #include <algorithm>
 
 #include "runtime_internal.h"
@@ -83,6 +86,17 @@ int history_reset(AccumState &a, const CameraModel &cam) {
     return 0;
 }
 
+int clamp_enable(AccumState &a, const CameraModel &cam, bool on, const RtClampOptions &o) {
+    std::unique_lock<std::recursive_mutex> lock;
+    if (!accum_begin(a, cam, lock)) return -1;
+    // (no snapshot goes: a resolve is a function of prev, the accumulator's state and the options)
+    a.clamp_enabled = on;
+    a.clamp_gamma = on ? o.gamma : 0.0f;
+    a.clamp_radius = on ? (uint32_t)o.radius : 0u;
+    a.clamp_flags = on ? o.flags : 0u;
+    return 0;
+}
+
 int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOptions *filter, float *out_rgb,
                     void *out_rgba, bool on_device, hipStream_t stream, const char *who) {
     if (!ap || !cam) return fail(who, "null accumulator");
@@ -123,10 +137,15 @@ int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOption
     // ... and after the filter's last run (its staging is written below)
     if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
 
-    // a snapshot of another scene: both go; a cur of another camera becomes prev
+    // a snapshot of another scene: both go; a cur of another camera becomes prev.
+    // Under a clamp that keeps history over edits (only materials can be edited:
+    // the guides stay true) they stay, and a cur of another scene becomes prev too
+    const bool keep = a.clamp_enabled && (a.clamp_flags & RT_CLAMP_KEEP_ON_EDIT) != 0;
     for (const auto &h : a.hist)
-        if (h.valid && h.edit != a.edit_version) drop_snapshots(a);
-    if (a.hist[a.hist_cur].valid && std::memcmp(a.hist[a.hist_cur].cam, a.cam, sizeof(a.cam)) != 0) a.hist_cur ^= 1u;
+        if (!keep && h.valid && h.edit != a.edit_version) drop_snapshots(a);
+    if (a.hist[a.hist_cur].valid && (std::memcmp(a.hist[a.hist_cur].cam, a.cam, sizeof(a.cam)) != 0 ||
+                                     (keep && a.hist[a.hist_cur].edit != a.edit_version)))
+        a.hist_cur ^= 1u;
     AccumState::HistorySnap &cur = a.hist[a.hist_cur], &prev = a.hist[a.hist_cur ^ 1u];
     // (valid again once the kernel that fills it is enqueued)
     cur.valid = false;
@@ -159,7 +178,8 @@ int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOption
     k.out_rgba = filter ? nullptr : d_rgba;
     k.width = (uint32_t)a.width;
     k.height = (uint32_t)a.height;
-    HIP_TRY(launch_history_resolve(k, s));
+    const HistoryClamp clamp{a.clamp_gamma, a.clamp_radius, nullptr};
+    HIP_TRY(a.clamp_enabled ? launch_history_clamp(k, clamp, s) : launch_history_resolve(k, s));
     std::memcpy(cur.cam, a.cam, sizeof(a.cam));
     cur.edit = a.edit_version;
     cur.valid = true;
@@ -203,9 +223,9 @@ int history_read_length(AccumState &a, const CameraModel &cam, float *len) {
 
 int history_run(size_t width, size_t height, float max_history, float sigma_z, const float *prev_cam,
                 const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
-                const void *records, float *out_rgbl, int device) {
-    // (the arguments were checked by rt_history_run)
-    const char *who = "rt_history_run";
+                const void *records, float *out_rgbl, int device, const RtClampOptions *clamp, float *out_box) {
+    // (the arguments were checked by rt_history_run or rt_clamp_run)
+    const char *who = clamp ? "rt_clamp_run" : "rt_history_run";
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
         set_error(std::string(who) + ": no HIP device available: the MI355X render path requires a GPU");
@@ -254,8 +274,19 @@ int history_run(size_t width, size_t height, float max_history, float sigma_z, c
     k.width = (uint32_t)width;
     k.height = (uint32_t)height;
     // (the null stream: the copies above are done, the one below follows the kernel)
-    HIP_TRY(launch_history_resolve(k, nullptr));
+    DevBuf<float> d_box;
+    HistoryClamp c{};
+    if (clamp) {
+        c.gamma = clamp->gamma;
+        c.radius = (uint32_t)clamp->radius;
+        if (out_box) {
+            HIP_TRY(d_box.grow(6 * npix));
+            c.out_box = d_box.get();
+        }
+    }
+    HIP_TRY(clamp ? launch_history_clamp(k, c, nullptr) : launch_history_resolve(k, nullptr));
     HIP_TRY(hipMemcpy(out_rgbl, d_out.get(), npix * sizeof(float4), hipMemcpyDeviceToHost));
+    if (c.out_box) HIP_TRY(hipMemcpy(out_box, d_box.get(), 6 * npix * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

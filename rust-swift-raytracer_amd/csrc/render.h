@@ -422,6 +422,21 @@ struct HistoryResolve {
     uint32_t width, height;
 };
 hipError_t launch_history_resolve(const HistoryResolve &a, hipStream_t stream);
+// The neighbourhood clamp inside step 5 (rt_clamp_*, clamp.hip):
+// history_clamp_kernel runs instead of history_resolve_kernel --
+// the same lanes and tiles; each lane that may take history also gathers the
+// (2 radius + 1)^2 means around it (from rgb, or the three sums planes and
+// count), folds their first and second moments and clamps hc to
+// mu -+ gamma * sqrt(var) before the blend.  out_box (may be null): 6 f32 per
+// pixel {lo.rgb, hi.rgb}, for every pixel.  The fields live in a struct of
+// their own: HistoryResolve is the unclamped kernel's argument block, which
+// stays byte for byte what it was.
+struct HistoryClamp {
+    float gamma;
+    uint32_t radius;  // 1 .. 3
+    float *out_box;
+};
+hipError_t launch_history_clamp(const HistoryResolve &a, const HistoryClamp &c, hipStream_t stream);
 // The adaptive accumulator's list kernels (adapt.hip).  iota: list[i] = i.
 // select: one thread per entry i < n of list: count[list[i]] = N and, with
 // decide, keep[i] = 0 iff the pixel converged by the rule of DESIGN.md 5.7

@@ -322,6 +322,11 @@ struct AccumState {
     HistorySnap hist[2];
     uint32_t hist_cur = 0;
     DevBuf<float> hist_rgb;
+    // The neighbourhood clamp of a resolve (rt_clamp_*): a
+    // setting only, which outlives the history's enable, disable and reset.
+    bool clamp_enabled = false;
+    float clamp_gamma = 0.0f;
+    uint32_t clamp_radius = 0, clamp_flags = 0;
 };
 
 // One pass of an accumulation, for render_frame: n0 samples held, the frame's
@@ -442,9 +447,14 @@ int history_reset(AccumState &a, const CameraModel &cam);
 int history_resolve(AccumState *a, const CameraModel *cam, const RtFilterOptions *filter, float *out_rgb,
                     void *out_rgba, bool on_device, hipStream_t stream, const char *who);
 int history_read_length(AccumState &a, const CameraModel &cam, float *len);
+// (run with clamp: rt_clamp_run, the clamped step 5 and, with out_box, every pixel's box)
 int history_run(size_t width, size_t height, float max_history, float sigma_z, const float *prev_cam,
                 const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
-                const void *records, float *out_rgbl, int device);
+                const void *records, float *out_rgbl, int device, const RtClampOptions *clamp = nullptr,
+                float *out_box = nullptr);
+// The resolve's neighbourhood clamp (rt_clamp_*): the setting
+// (on false: off); it drops no snapshot.  The options were checked by the caller.
+int clamp_enable(AccumState &a, const CameraModel &cam, bool on, const RtClampOptions &o);
 // Waits for device d's pending counted frame and fills stats from it.
 int collect_frame_stats(DeviceState *d, RtRenderStats *stats);
 

@@ -25,6 +25,7 @@ FLAG_SERIAL_CHECK = 2
 DEFAULT_SEED = 2547549
 VIEW_NORMAL, VIEW_DEPTH, VIEW_ALBEDO, VIEW_PRIM = 0, 1, 2, 3
 FILTER_SAME_PRIM = 1
+CLAMP_KEEP_ON_EDIT = 1
 
 # Every symbol declared in include/raytracer.h and include/raytracer_amd.h.
 EXPORTS = (
@@ -47,6 +48,7 @@ EXPORTS = (
     "rt_filter_run", "rt_filter_accum", "rt_filter_accum_device",
     "rt_history_default_options", "rt_history_enable", "rt_history_disable", "rt_history_reset",
     "rt_history_resolve", "rt_history_resolve_device", "rt_history_read_length", "rt_history_run",
+    "rt_clamp_default_options", "rt_clamp_enable", "rt_clamp_disable", "rt_clamp_run",
 )
 
 
@@ -109,6 +111,11 @@ class FilterOptions(C.Structure):
 class HistoryOptions(C.Structure):
     """raytracer_amd.h RtHistoryOptions (defaults: 32, 0.02)."""
     _fields_ = [("max_history", C.c_float), ("sigma_z", C.c_float)]
+
+
+class ClampOptions(C.Structure):
+    """raytracer_amd.h RtClampOptions (defaults: 1.5, 1, 0)."""
+    _fields_ = [("gamma", C.c_float), ("radius", C.c_int32), ("flags", C.c_uint32)]
 
 
 class RenderStats(C.Structure):
@@ -316,6 +323,17 @@ def lib(path=None):
             L.rt_history_read_length.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_history_run.restype = C.c_int
             L.rt_history_run.argtypes = [C.c_size_t, C.c_size_t, HO] + [C.c_void_p] * 7 + [C.c_int]
+        if hasattr(L, "rt_clamp_enable"):  # (likewise)
+            HO = C.POINTER(HistoryOptions)
+            CO = C.POINTER(ClampOptions)
+            L.rt_clamp_default_options.restype = None
+            L.rt_clamp_default_options.argtypes = [CO]
+            L.rt_clamp_enable.restype = C.c_int
+            L.rt_clamp_enable.argtypes = [C.c_void_p, CO]
+            L.rt_clamp_disable.restype = C.c_int
+            L.rt_clamp_disable.argtypes = [C.c_void_p]
+            L.rt_clamp_run.restype = C.c_int
+            L.rt_clamp_run.argtypes = [C.c_size_t, C.c_size_t, HO, CO] + [C.c_void_p] * 8 + [C.c_int]
         _libs[path] = L
     return _libs[path]
 
@@ -821,6 +839,16 @@ class Accumulator:
         self._check(self._L.rt_history_read_length(self._a, out.ctypes.data), "rt_history_read_length")
         return out
 
+    # ---- the resolve's neighbourhood clamp (rt_clamp_*)
+    def clamp_enable(self, **opts):
+        """rt_clamp_enable with the defaults overridden (gamma, radius, flags;
+        keep_on_edit=True sets CLAMP_KEEP_ON_EDIT); drops no snapshot."""
+        o = clamp_options(self._L, **opts)
+        self._check(self._L.rt_clamp_enable(self._a, C.byref(o)), "rt_clamp_enable")
+
+    def clamp_disable(self):
+        self._check(self._L.rt_clamp_disable(self._a), "rt_clamp_disable")
+
     def active_list(self):
         """The active list: uint32 frame indices (row * width + col, top row first), ascending."""
         out = np.zeros(self.width * self.height, np.uint32)
@@ -883,6 +911,55 @@ def history_run(rgb, n, records, prev_cam=None, prev_rgbl=None, prev_records=Non
     if rc != 0:
         raise RenderError(f"rt_history_run failed ({rc}): {L.rt_last_error().decode()}")
     return out
+
+
+def clamp_options(L=None, **opts):
+    """rt_clamp_default_options with the fields given overridden (gamma, radius,
+    flags; keep_on_edit=True sets CLAMP_KEEP_ON_EDIT)."""
+    o = ClampOptions()
+    (L or lib()).rt_clamp_default_options(C.byref(o))
+    if opts.pop("keep_on_edit", False):
+        o.flags |= CLAMP_KEEP_ON_EDIT
+    for k, v in opts.items():
+        if k not in ("gamma", "radius", "flags"):
+            raise TypeError(f"unknown clamp option {k!r}")
+        setattr(o, k, (o.flags | v) if k == "flags" else v)
+    return o
+
+
+def clamp_run(rgb, n, records, prev_cam=None, prev_rgbl=None, prev_records=None, clamp=None, box=True, device=-1,
+              L=None, **opts):
+    """rt_clamp_run: rt_history_run with the neighbourhood clamp.  The arrays as
+    history_run's; clamp: a dict of clamp_options fields (None: the defaults); opts:
+    history_options fields -> (rgbl float32[height, width, 4], box float32[height,
+    width, 6] {lo.rgb, hi.rgb} of every pixel, or None with box=False)."""
+    L = L or lib()
+    o = history_options(L, **opts)
+    co = clamp_options(L, **(clamp or {}))
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("rgb is height x width x 3 floats")
+    h, w = c.shape[:2]
+    cnt = np.ascontiguousarray(n, dtype=np.uint32)
+    g = np.ascontiguousarray(records, dtype=FIRST_HIT_DTYPE)
+    if cnt.size != w * h or g.size != w * h:
+        raise ValueError("n and records are height x width")
+    pc = pl = pg = None
+    if prev_rgbl is not None:
+        pc = np.ascontiguousarray(prev_cam, dtype=np.float32)
+        pl = np.ascontiguousarray(prev_rgbl, dtype=np.float32)
+        pg = np.ascontiguousarray(prev_records, dtype=FIRST_HIT_DTYPE)
+        if pc.size != 12 or pl.size != 4 * w * h or pg.size != w * h:
+            raise ValueError("prev_cam is 12 floats, prev_rgbl height x width x 4, prev_records height x width")
+    out = np.zeros((h, w, 4), np.float32)
+    out_box = np.zeros((h, w, 6), np.float32) if box else None
+    rc = L.rt_clamp_run(w, h, C.byref(o), C.byref(co),
+                        *(a.ctypes.data if a is not None else None for a in (pc, pl, pg)),
+                        c.ctypes.data, cnt.ctypes.data, g.ctypes.data, out.ctypes.data,
+                        out_box.ctypes.data if box else None, device)
+    if rc != 0:
+        raise RenderError(f"rt_clamp_run failed ({rc}): {L.rt_last_error().decode()}")
+    return out, out_box
 
 
 class Filter:
