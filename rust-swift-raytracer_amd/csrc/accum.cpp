@@ -37,11 +37,8 @@ void accum_check_state(AccumState &a, WorldState &w, const float cam[12]) {
 }
 
 void accum_release(AccumState *a) {
-    if (a->device >= 0 && hipSetDevice(a->device) == hipSuccess) {
-        // (the last pass may still write the buffers that delete frees)
-        if (a->done_stream) (void)hipEventSynchronize(a->done);
-        if (a->done) (void)hipEventDestroy(a->done);
-    }
+    // (the last pass may still write the buffers that delete frees)
+    if (a->device >= 0 && hipSetDevice(a->device) == hipSuccess) (void)a->done.sync();
     delete a;
 }
 }  // namespace
@@ -102,21 +99,19 @@ AccumState *accum_create(WorldState &w, size_t width, size_t height, uint32_t st
     a->width = width; a->height = height; a->stride = stride;
     a->depth = depth; a->device = d->device; a->accel = accel;
     a->mode = mode; a->seed = seed;
-    auto fail = [&](hipError_t e, const char *what) -> AccumState * {
+    auto give_up = [&](hipError_t e, const char *what) -> AccumState * {
         set_error(std::string("rt_accum_create: ") + what + " failed: " + hipGetErrorString(e));
         accum_release(a);
         return nullptr;
     };
-    hipError_t e = hipEventCreateWithFlags(&a->done, hipEventDisableTiming);
-    if (e != hipSuccess) return fail(e, "hipEventCreate");
-    e = a->sums.grow(3 * width * height);
-    if (e != hipSuccess) return fail(e, "allocating the sums");
+    hipError_t e = a->sums.grow(3 * width * height);
+    if (e != hipSuccess) return give_up(e, "allocating the sums");
     if (mode == RT_RNG_REPLAY) {
         const size_t n = width * height * (size_t)stride;
         e = a->replay.grow(n);
-        if (e != hipSuccess) return fail(e, "allocating the replay table");
+        if (e != hipSuccess) return give_up(e, "allocating the replay table");
         e = hipMemcpy(a->replay.get(), replay_states, n * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(e, "hipMemcpy (replay table)");
+        if (e != hipSuccess) return give_up(e, "hipMemcpy (replay table)");
     }
     std::lock_guard<std::mutex> g(g_accum_mu);
     a->world = &w;
@@ -156,7 +151,7 @@ int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t 
     DeviceState *d = nullptr;
     int rc = device_for(w, a.device, d);
     if (rc) return rc;
-    hipStream_t s = stream ? stream : d->stream;
+    hipStream_t s = stream ? stream : d->stream.get();
     const size_t npix = a.width * a.height;
     // (an adaptive accumulator's passes write its own frame, which is copied out below)
     uint32_t *const d_user = d_out;
@@ -213,8 +208,7 @@ int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t 
                                              a.list[a.cur ^ 1u].get(), a.d_len.get(), s));
                 HIP_TRY(hipMemcpyAsync(a.h_len.get(), a.d_len.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             }
-            HIP_TRY(hipEventRecord(a.done, s));
-            a.done_stream = s;
+            HIP_TRY(a.done.record(s));
             if (decide) {
                 HIP_TRY(hipStreamSynchronize(s));
                 a.cur ^= 1u;
@@ -235,7 +229,7 @@ int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t 
     if (stats) *stats = total;
     if (a.adaptive) {
         // (a call that traced nothing still orders the copies after the last pass)
-        if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
+        HIP_TRY(a.done.wait(s));
         if (d_user) HIP_TRY(hipMemcpyAsync(d_user, a.frame.get(), npix * 4, hipMemcpyDeviceToDevice, s));
     }
     if (host_out) {
@@ -269,7 +263,7 @@ int accum_read(AccumState &a, const CameraModel &cam, float *sums) {
         return 0;
     }
     HIP_TRY(hipSetDevice(a.device));
-    HIP_TRY(hipEventSynchronize(a.done));
+    HIP_TRY(a.done.sync());
     std::vector<float> planes(3 * npix);
     HIP_TRY(hipMemcpy(planes.data(), a.sums.get(), 3 * npix * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < npix; ++i)
@@ -360,7 +354,7 @@ int adapt_read_plane(AccumState &a, const CameraModel &cam, bool counts, void *o
         return 0;
     }
     HIP_TRY(hipSetDevice(a.device));
-    HIP_TRY(hipEventSynchronize(a.done));
+    HIP_TRY(a.done.sync());
     HIP_TRY(hipMemcpy(out, counts ? (const void *)a.count.get() : (const void *)a.sumsq.get(), npix * 4,
                       hipMemcpyDeviceToHost));
     return 0;
@@ -387,7 +381,7 @@ long adapt_read_active(AccumState &a, const CameraModel &cam, uint32_t *list, si
     const size_t n = std::min<size_t>(cap, a.nactive);
     if (list && n) {
         HIP_TRY(hipSetDevice(a.device));
-        HIP_TRY(hipEventSynchronize(a.done));
+        HIP_TRY(a.done.sync());
         HIP_TRY(hipMemcpy(list, a.list[a.cur].get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return (long)a.nactive;

@@ -9,7 +9,7 @@
 
 #include "../../include/raytracer.h"
 #include "../../include/raytracer_amd.h"
-#include "runtime.h"
+#include "runtime_internal.h"  // (the shared argument checks)
 #include "scene.h"
 
 // The opaque types of raytracer.h.  Rust_WorldHandle stays two pointers;
@@ -446,19 +446,10 @@ namespace {
 class AccumCall {
 public:
     AccumCall(const RtAccum *acc, const char *who) {
-        if (!acc || !acc->state) {
-            rtamd::set_error(std::string(who) + ": null accumulator");
-            return;
-        }
+        if (!acc || !acc->state) { rtamd::fail(who, "null accumulator"); return; }
         world_ = rtamd::accum_enter(*acc->state);
-        if (!world_) {
-            rtamd::set_error(std::string(who) + ": the accumulator's world was freed");
-            return;
-        }
-        if (!acc->handle->camera) {
-            rtamd::set_error(std::string(who) + ": null camera");
-            return;
-        }
+        if (!world_) { rtamd::fail(who, "the accumulator's world was freed"); return; }
+        if (!acc->handle->camera) { rtamd::fail(who, "null camera"); return; }
         cam_ = &acc->handle->camera->cam;
     }
     ~AccumCall() {
@@ -522,15 +513,9 @@ int rt_adapt_enable(RtAccum *acc, const RtAdaptOptions *opts) {
     if (opts) o = *opts;
     else rt_adapt_default_options(&o);
     // (the options first: a caller's mistake shows whatever the accumulator's state)
-    if (!(o.tolerance >= 0.0f) || !(o.tolerance <= 3.4028234663852886e38f) || !(o.bias >= 0.0f) ||
-        !(o.bias <= 3.4028234663852886e38f)) {
-        rtamd::set_error("rt_adapt_enable: tolerance and bias must be finite and >= 0");
-        return -1;
-    }
-    if (o.min_samples < 2) {
-        rtamd::set_error("rt_adapt_enable: min_samples must be at least 2");
-        return -1;
-    }
+    if (!rtamd::finite_from(o.tolerance, 0.0f) || !rtamd::finite_from(o.bias, 0.0f))
+        return rtamd::fail("rt_adapt_enable", "tolerance and bias must be finite and >= 0");
+    if (o.min_samples < 2) return rtamd::fail("rt_adapt_enable", "min_samples must be at least 2");
     const AccumCall call(acc, "rt_adapt_enable");
     if (!call) return -1;
     return rtamd::adapt_enable(*acc->state, call.cam(), o.tolerance, o.bias, o.min_samples);
@@ -574,10 +559,7 @@ void rt_first_hit_default_options(RtFirstHitOptions *o) {
 static int first_hit_call(const Rust_WorldHandle *h, size_t width, size_t height, const RtFirstHitOptions *opts,
                           bool views, int view, void *d_out, void *hip_stream, void *host_out, const char *who,
                           const rtamd::FirstHitPick *pick = nullptr) {
-    if (!h || !h->world || !h->camera) {
-        rtamd::set_error(std::string(who) + ": null world handle");
-        return -1;
-    }
+    if (!h || !h->world || !h->camera) return rtamd::fail(who, "null world handle");
     return rtamd::first_hit(h->world->state, h->camera->cam, width, height, opts, views, view, d_out,
                             static_cast<hipStream_t>(hip_stream), host_out, who, pick);
 }
@@ -662,26 +644,39 @@ void rt_history_default_options(RtHistoryOptions *o) {
 }
 
 namespace {
-// the options (null: the defaults), checked; false with the error set
-bool history_options(const RtHistoryOptions *opts, const char *who, RtHistoryOptions &o) {
+// the options (null: the defaults), checked; -1 with the error set
+int history_options(const RtHistoryOptions *opts, const char *who, RtHistoryOptions &o) {
     if (opts) o = *opts;
     else rt_history_default_options(&o);
-    if (!(o.max_history >= 1.0f) || !(o.max_history <= 3.4028234663852886e38f)) {
-        rtamd::set_error(std::string(who) + ": max_history must be finite and >= 1");
-        return false;
-    }
-    if (!(o.sigma_z > 0.0f) || !(o.sigma_z <= 3.4028234663852886e38f)) {
-        rtamd::set_error(std::string(who) + ": sigma_z must be finite and > 0");
-        return false;
-    }
-    return true;
+    if (!rtamd::finite_from(o.max_history, 1.0f)) return rtamd::fail(who, "max_history must be finite and >= 1");
+    if (!rtamd::finite_from(o.sigma_z, 0.0f, true)) return rtamd::fail(who, "sigma_z must be finite and > 0");
+    return 0;
+}
+int clamp_options(const RtClampOptions *opts, const char *who, RtClampOptions &o);
+
+// rt_history_run's and rt_clamp_run's arguments: the size, the history's options
+// -> o, the clamp's -> *c (c null: rt_history_run, none), the arrays
+int history_run_check(const char *who, size_t width, size_t height, const RtHistoryOptions *opts, RtHistoryOptions &o,
+                      const RtClampOptions *clamp, RtClampOptions *c, const float *prev_cam, const float *prev_rgbl,
+                      const RtFirstHit *prev_records, const float *rgb, const uint32_t *n, const RtFirstHit *records,
+                      const float *out_rgbl) {
+    if (rtamd::check_image_size(width, height, "image size", who)) return -1;
+    if (history_options(opts, who, o)) return -1;
+    if (c && clamp_options(clamp, who, *c)) return -1;
+    if (prev_rgbl && !prev_cam) return rtamd::fail(who, "null input: prev_cam (with prev_rgbl given)");
+    if (prev_rgbl && !prev_records) return rtamd::fail(who, "null input: prev_records (with prev_rgbl given)");
+    if (!rgb) return rtamd::fail(who, "null input: rgb");
+    if (!n) return rtamd::fail(who, "null input: n");
+    if (!records) return rtamd::fail(who, "null input: records");
+    if (!out_rgbl) return rtamd::fail(who, "null output: out_rgbl");
+    return 0;
 }
 }  // namespace
 
 int rt_history_enable(RtAccum *acc, const RtHistoryOptions *opts) {
     // (the options first: a caller's mistake shows whatever the accumulator's state)
     RtHistoryOptions o;
-    if (!history_options(opts, "rt_history_enable", o)) return -1;
+    if (history_options(opts, "rt_history_enable", o)) return -1;
     const AccumCall call(acc, "rt_history_enable");
     if (!call) return -1;
     return rtamd::history_enable(*acc->state, call.cam(), true, o.max_history, o.sigma_z);
@@ -722,22 +717,10 @@ int rt_history_read_length(RtAccum *acc, float *len) {
 int rt_history_run(size_t width, size_t height, const RtHistoryOptions *opts, const float *prev_cam,
                    const float *prev_rgbl, const RtFirstHit *prev_records, const float *rgb, const uint32_t *n,
                    const RtFirstHit *records, float *out_rgbl, int device) {
-    const char *who = "rt_history_run";
-    auto fail = [&](const char *msg) {
-        rtamd::set_error(std::string(who) + ": " + msg);
-        return -1;
-    };
-    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
-        (uint64_t)width * height >= (1ull << 31))
-        return fail("image size: width and height at least 1, width * height below 2^31");
     RtHistoryOptions o;
-    if (!history_options(opts, who, o)) return -1;
-    if (prev_rgbl && !prev_cam) return fail("null input: prev_cam (with prev_rgbl given)");
-    if (prev_rgbl && !prev_records) return fail("null input: prev_records (with prev_rgbl given)");
-    if (!rgb) return fail("null input: rgb");
-    if (!n) return fail("null input: n");
-    if (!records) return fail("null input: records");
-    if (!out_rgbl) return fail("null output: out_rgbl");
+    if (history_run_check("rt_history_run", width, height, opts, o, nullptr, nullptr, prev_cam, prev_rgbl, prev_records,
+                          rgb, n, records, out_rgbl))
+        return -1;
     return rtamd::history_run(width, height, o.max_history, o.sigma_z, prev_cam, prev_rgbl, prev_records, rgb, n,
                               records, out_rgbl, device);
 }
@@ -750,30 +733,21 @@ void rt_clamp_default_options(RtClampOptions *o) {
 }
 
 namespace {
-// the options (null: the defaults), checked; false with the error set
-bool clamp_options(const RtClampOptions *opts, const char *who, RtClampOptions &o) {
+// the options (null: the defaults), checked; -1 with the error set
+int clamp_options(const RtClampOptions *opts, const char *who, RtClampOptions &o) {
     if (opts) o = *opts;
     else rt_clamp_default_options(&o);
-    if (!(o.gamma >= 0.0f) || !(o.gamma <= 3.4028234663852886e38f)) {
-        rtamd::set_error(std::string(who) + ": gamma must be finite and >= 0");
-        return false;
-    }
-    if (o.radius < 1 || o.radius > 3) {
-        rtamd::set_error(std::string(who) + ": radius must be 1 .. 3");
-        return false;
-    }
-    if (o.flags & ~(uint32_t)RT_CLAMP_KEEP_ON_EDIT) {
-        rtamd::set_error(std::string(who) + ": flags: unknown bits");
-        return false;
-    }
-    return true;
+    if (!rtamd::finite_from(o.gamma, 0.0f)) return rtamd::fail(who, "gamma must be finite and >= 0");
+    if (o.radius < 1 || o.radius > 3) return rtamd::fail(who, "radius must be 1 .. 3");
+    if (o.flags & ~(uint32_t)RT_CLAMP_KEEP_ON_EDIT) return rtamd::fail(who, "flags: unknown bits");
+    return 0;
 }
 }  // namespace
 
 int rt_clamp_enable(RtAccum *acc, const RtClampOptions *opts) {
     // (the options first, as rt_history_enable)
     RtClampOptions o;
-    if (!clamp_options(opts, "rt_clamp_enable", o)) return -1;
+    if (clamp_options(opts, "rt_clamp_enable", o)) return -1;
     const AccumCall call(acc, "rt_clamp_enable");
     if (!call) return -1;
     return rtamd::clamp_enable(*acc->state, call.cam(), true, o);
@@ -787,24 +761,11 @@ int rt_clamp_disable(RtAccum *acc) {
 int rt_clamp_run(size_t width, size_t height, const RtHistoryOptions *opts, const RtClampOptions *clamp,
                  const float *prev_cam, const float *prev_rgbl, const RtFirstHit *prev_records, const float *rgb,
                  const uint32_t *n, const RtFirstHit *records, float *out_rgbl, float *out_box, int device) {
-    const char *who = "rt_clamp_run";
-    auto fail = [&](const char *msg) {
-        rtamd::set_error(std::string(who) + ": " + msg);
-        return -1;
-    };
-    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
-        (uint64_t)width * height >= (1ull << 31))
-        return fail("image size: width and height at least 1, width * height below 2^31");
     RtHistoryOptions o;
-    if (!history_options(opts, who, o)) return -1;
     RtClampOptions c;
-    if (!clamp_options(clamp, who, c)) return -1;
-    if (prev_rgbl && !prev_cam) return fail("null input: prev_cam (with prev_rgbl given)");
-    if (prev_rgbl && !prev_records) return fail("null input: prev_records (with prev_rgbl given)");
-    if (!rgb) return fail("null input: rgb");
-    if (!n) return fail("null input: n");
-    if (!records) return fail("null input: records");
-    if (!out_rgbl) return fail("null output: out_rgbl");
+    if (history_run_check("rt_clamp_run", width, height, opts, o, clamp, &c, prev_cam, prev_rgbl, prev_records, rgb, n,
+                          records, out_rgbl))
+        return -1;
     return rtamd::history_run(width, height, o.max_history, o.sigma_z, prev_cam, prev_rgbl, prev_records, rgb, n,
                               records, out_rgbl, device, &c, out_box);
 }

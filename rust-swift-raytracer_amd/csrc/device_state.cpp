@@ -16,24 +16,13 @@ void set_error(const std::string &msg) { g_error = msg; }
 const std::string &last_error() { return g_error; }
 
 DeviceState::~DeviceState() {
-    if (device < 0) return;
-    if (hipSetDevice(device) != hipSuccess) return;
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : tev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : sev)
-        if (e) (void)hipEventDestroy(e);
-    if (done) (void)hipEventDestroy(done);
-    if (stream) (void)hipStreamDestroy(stream);
-    // (the buffers free themselves next, as members, on this device)
+    // (the events, the stream and the buffers go next, as members, on this device)
+    if (device >= 0) (void)hipSetDevice(device);
 }
 
 static int create_stream_and_events(DeviceState *d) {
-    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    for (auto &e : d->ev) HIP_TRY(hipEventCreate(&e));
-    for (auto &e : d->sev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&d->done, hipEventDisableTiming));
+    HIP_TRY(d->stream.create());
+    for (auto &e : d->sev) HIP_TRY(e.create(true));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, d->device));
     d->num_cus = prop.multiProcessorCount;
@@ -249,24 +238,32 @@ static int choose_lds_layout(const WorldState &w, DeviceState *d, size_t lds_cap
     return 0;
 }
 
-int device_for(WorldState &w, int want, DeviceState *&out) {
+int select_device(int want, int &dev, const char *who) {
+    const std::string prefix = who ? std::string(who) + ": " : std::string();
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_error("no HIP device available: the MI355X render path requires a GPU");
+        set_error(prefix + "no HIP device available: the MI355X render path requires a GPU");
         return -3;
     }
-    int dev = want;
+    dev = want;
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
     if (dev >= count) {
-        set_error("device ordinal out of range");
+        set_error(prefix + "device ordinal out of range");
         return -1;
     }
     HIP_TRY(hipSetDevice(dev));
+    return 0;
+}
+
+int device_for(WorldState &w, int want, DeviceState *&out) {
+    int dev = -1;
+    int rc = select_device(want, dev);
+    if (rc) return rc;
     auto &slot = w.devices[dev];
     if (!slot) {
         auto d = std::make_unique<DeviceState>();
         d->device = dev;
-        int rc = create_stream_and_events(d.get());
+        rc = create_stream_and_events(d.get());
         if (rc) return rc;
         // LDS trees above 64 KB per workgroup need the kernels' opt-in, before
         // any occupancy query or launch; a runtime that refuses it keeps the

@@ -11,30 +11,12 @@
 
 namespace rtamd {
 
-namespace {
-
-constexpr float kMaxFloat = 3.4028234663852886e38f;
-
-int fail(const char *who, const std::string &msg) {
-    set_error(std::string(who) + ": " + msg);
-    return -1;
-}
-
-int check_size(size_t width, size_t height, const char *who) {
-    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
-        (uint64_t)width * height >= (1ull << 31))
-        return fail(who, "image size: width and height at least 1, width * height below 2^31");
-    return 0;
-}
-
-}  // namespace
-
 int filter_check_options(const RtFilterOptions *opts, const char *who, RtFilterOptions &o) {
     if (opts) o = *opts;
     else rt_filter_default_options(&o);
     if (o.levels < 0 || o.levels > 8) return fail(who, "levels must be 0 to 8");
-    if (!(o.sigma_l > 0.0f) || !(o.sigma_l <= kMaxFloat)) return fail(who, "sigma_l must be finite and > 0");
-    if (!(o.sigma_z > 0.0f) || !(o.sigma_z <= kMaxFloat)) return fail(who, "sigma_z must be finite and > 0");
+    if (!finite_from(o.sigma_l, 0.0f, true)) return fail(who, "sigma_l must be finite and > 0");
+    if (!finite_from(o.sigma_z, 0.0f, true)) return fail(who, "sigma_z must be finite and > 0");
     if (o.normal_squarings < 0 || o.normal_squarings > 8) return fail(who, "normal_squarings must be 0 to 8");
     if (o.flags & ~(uint32_t)RT_FILTER_SAME_PRIM) return fail(who, "flags: unknown bits (RT_FILTER_SAME_PRIM is 1)");
     return 0;
@@ -50,12 +32,11 @@ int filter_check_outputs(const void *out_rgb, const void *out_rgba, const char *
 int filter_enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, float *d_out_rgb, uint32_t *d_out_rgba,
                    hipStream_t s) {
     const size_t npix = f.width * f.height;
-    if (!f.done) HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
     HIP_TRY(f.col[0].grow(npix));
     if (o.levels >= 2) HIP_TRY(f.col[1].grow(npix));
     HIP_TRY(f.g0.grow(npix));
     HIP_TRY(f.g1.grow(npix));
-    if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
+    HIP_TRY(f.done.wait(s));
     src.sigma_z = o.sigma_z;
     src.col = f.col[0].get();
     src.g0 = f.g0.get();
@@ -79,8 +60,7 @@ int filter_enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, flo
         lv.sl = std::ldexp(o.sigma_l, -l);  // sigma_l * 2^-l
         HIP_TRY(launch_filter_level(lv, s));
     }
-    HIP_TRY(hipEventRecord(f.done, s));
-    f.done_stream = s;
+    HIP_TRY(f.done.record(s));
     return 0;
 }
 
@@ -110,16 +90,13 @@ int filter_fetch_outputs(FilterState &f, float *out_rgb, void *out_rgba, hipStre
 }
 
 FilterState::~FilterState() {
-    if (device >= 0 && (done || stream) && hipSetDevice(device) == hipSuccess) {
-        // (the last run may still use the buffers that the members free)
-        if (done_stream) (void)hipEventSynchronize(done);
-        if (done) (void)hipEventDestroy(done);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    // (a filter that never ran makes no HIP call; the last run may still use
+    // the buffers that the members free)
+    if (device >= 0 && (done.recorded() || stream) && hipSetDevice(device) == hipSuccess) (void)done.sync();
 }
 
 FilterState *filter_create(size_t width, size_t height, int device) {
-    if (check_size(width, height, "rt_filter_create")) return nullptr;
+    if (check_image_size(width, height, "image size", "rt_filter_create")) return nullptr;
     FilterState *f = new FilterState();
     f->width = width;
     f->height = height;
@@ -139,20 +116,14 @@ int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, co
     if (rc) return rc;
 
     std::lock_guard<std::mutex> lock(f->mu);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_error(std::string(who) + ": no HIP device available: the MI355X render path requires a GPU");
-        return -3;
-    }
-    int dev = f->device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    if (dev >= count) return fail(who, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(dev));
+    int dev = -1;
+    rc = select_device(f->device, dev, who);
+    if (rc) return rc;
     f->device = dev;  // (the scratch lives there from now on)
     hipStream_t s = on_device ? stream : nullptr;
     if (!s) {
-        if (!f->stream) HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
-        s = f->stream;
+        HIP_TRY(f->stream.create());
+        s = f->stream.get();
     }
     const size_t npix = f->width * f->height;
     FilterPack src{};
@@ -167,7 +138,7 @@ int filter_run(FilterState *f, const RtFilterOptions *opts, const float *rgb, co
         rc = filter_stage_outputs(*f, out_rgb, out_rgba, d_rgb, d_rgba);
         if (rc) return rc;
         // (the staging may still be read by the last run, on another stream)
-        if (f->done_stream && f->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f->done, 0));
+        HIP_TRY(f->done.wait(s));
         HIP_TRY(hipMemcpyAsync(f->in_rgb.get(), rgb, 3 * npix * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(f->in_rec.get(), records, npix * sizeof(RtFirstHit), hipMemcpyHostToDevice, s));
         src.rgb = f->in_rgb.get();
@@ -198,7 +169,7 @@ int accum_records(AccumState &a, WorldState &w, const CameraModel &cam, FilterSt
         a.rec_valid = false;
         HIP_TRY(a.records.grow(npix * (sizeof(RtFirstHit) / 4)));
         // (the last run, on another stream, may still read the old ones)
-        if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
+        HIP_TRY(f.done.wait(s));
         RtFirstHitOptions fo;
         rt_first_hit_default_options(&fo);
         fo.device = a.device;
@@ -221,51 +192,56 @@ int filter_accum(AccumState *ap, const CameraModel *cam, const RtFilterOptions *
     RtFilterOptions o;
     rc = filter_check_options(opts, who, o);
     if (rc) return rc;
-    if ((uint64_t)a.width * a.height >= (1ull << 31))
-        return fail(who, "the accumulator's frame has 2^31 pixels or more: the filter takes width * height below "
-                         "2^31 (an accumulator up to 2^32 - 1)");
-
-    std::unique_lock<std::recursive_mutex> lock;
-    WorldState *wp = accum_begin(a, *cam, lock);
-    if (!wp) return fail(who, "the accumulator's world was freed");
-    WorldState &w = *wp;
-    if (a.held == 0) return fail(who, "no samples held");
-    DeviceState *d = nullptr;
-    rc = device_for(w, a.device, d);
-    if (rc) return rc;
-    hipStream_t s = stream ? stream : d->stream;
-    const size_t npix = a.width * a.height;
-    FilterState &f = accum_filter(a);
-    std::lock_guard<std::mutex> flock(f.mu);
-    // d->done is recorded again below, on s: it must still stand for the frame
-    // another stream may be running, which the next frame on s has to wait for
-    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
-    // after the accumulator's last pass, like its other readers
-    if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
-
-    rc = accum_records(a, w, *cam, f, s, who);
+    AccumRead r{a, *cam, who, out_rgb, out_rgba, on_device};
+    rc = r.lock_world("the filter");
+    if (!rc) rc = r.begin(stream);
     if (rc) return rc;
 
     FilterPack src{};
     src.sums = a.sums.get();
-    src.plane = npix;
+    src.plane = a.width * a.height;
     src.count = a.adaptive ? a.count.get() : nullptr;
     src.held = a.held;
     src.records = reinterpret_cast<const float4 *>(a.records.get());
-    float *d_rgb = out_rgb;
-    uint32_t *d_rgba = static_cast<uint32_t *>(out_rgba);
-    if (!on_device) {
-        rc = filter_stage_outputs(f, out_rgb, out_rgba, d_rgb, d_rgba);
-        if (rc) return rc;
-    }
-    rc = filter_enqueue(f, o, src, d_rgb, d_rgba, s);
+    rc = filter_enqueue(*r.f, o, src, r.d_rgb, r.d_rgba, r.s);
+    return rc ? rc : r.finish();
+}
+
+int AccumRead::lock_world(const char *taker) {
+    if ((uint64_t)a.width * a.height >= (1ull << 31))
+        return fail(who, std::string("the accumulator's frame has 2^31 pixels or more: ") + taker +
+                             " takes width * height below 2^31 (an accumulator up to 2^32 - 1)");
+    w = accum_begin(a, cam, lock);
+    return w ? 0 : fail(who, "the accumulator's world was freed");
+}
+
+int AccumRead::begin(hipStream_t stream) {
+    if (a.held == 0) return fail(who, "no samples held");
+    int rc = device_for(*w, a.device, d);
     if (rc) return rc;
+    s = stream ? stream : d->stream.get();
+    f = &accum_filter(a);
+    flock = std::unique_lock<std::mutex>(f->mu);
+    // d->done is recorded again by finish, on s: it must still stand for the frame
+    // another stream may be running, which the next frame on s has to wait for ...
+    HIP_TRY(d->done.wait(s));
+    // ... after the accumulator's last pass, like its other readers, and its last
+    // resolve (the snapshots) ...
+    HIP_TRY(a.done.wait(s));
+    // ... and after the filter's last run (its scratch and staging are written next)
+    HIP_TRY(f->done.wait(s));
+    rc = accum_records(a, *w, cam, *f, s, who);
+    if (rc) return rc;
+    d_rgb = out_rgb;
+    d_rgba = static_cast<uint32_t *>(out_rgba);
+    return on_device ? 0 : filter_stage_outputs(*f, out_rgb, out_rgba, d_rgb, d_rgba);
+}
+
+int AccumRead::finish() {
     // the next pass, on whatever stream, writes the sums after this run read them
-    HIP_TRY(hipEventRecord(d->done, s));
-    d->done_stream = s;
-    HIP_TRY(hipEventRecord(a.done, s));
-    a.done_stream = s;
-    return on_device ? 0 : filter_fetch_outputs(f, out_rgb, out_rgba, s);
+    HIP_TRY(d->done.record(s));
+    HIP_TRY(a.done.record(s));
+    return on_device ? 0 : filter_fetch_outputs(*f, out_rgb, out_rgba, s);
 }
 
 }  // namespace rtamd

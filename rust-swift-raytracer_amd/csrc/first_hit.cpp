@@ -17,19 +17,12 @@ struct Request {
     uint32_t x0, y0, w, h;  // the rectangle, resolved
 };
 
-int fail(const char *who, const std::string &msg) {
-    set_error(std::string(who) + ": " + msg);
-    return -1;
-}
-
 // Every argument, with a message, before any device is looked for.
 int check_request(size_t width, size_t height, const RtFirstHitOptions *opts, int view, bool views,
                   const void *d_out, const void *host_out, const char *who, const FirstHitPick *pick,
                   Request &r) {
     if (!d_out && !host_out) return fail(who, "null output");
-    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
-        (uint64_t)width * height >= (1ull << 31))
-        return fail(who, "frame size: width and height at least 1, width * height below 2^31");
+    if (check_image_size(width, height, "frame size", who)) return -1;
     if (opts) r.o = *opts;
     else rt_first_hit_default_options(&r.o);
     const RtFirstHitOptions &o = r.o;
@@ -68,11 +61,11 @@ int first_hit(WorldState &w, const CameraModel &cam, size_t width, size_t height
     DeviceState *d = nullptr;
     rc = device_for(w, r.o.device, d);
     if (rc) return rc;
-    hipStream_t s = stream ? stream : d->stream;
+    hipStream_t s = stream ? stream : d->stream.get();
     // ordered against the frames and passes of other streams like a frame
     // (render_frame): the host path's buffer is the device's, and an edit's
     // re-upload must not overtake a launch that reads the old arrays
-    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
+    HIP_TRY(d->done.wait(s));
 
     // The scene and the camera as it is now.  The sphere tree and the static
     // triangle tree are exact for any origin; the primary strip lists (what
@@ -101,8 +94,7 @@ int first_hit(WorldState &w, const CameraModel &cam, size_t width, size_t height
     }
     const FirstHitTail tail{out, r.o.su, r.o.sv, r.x0, r.y0, r.w, r.h, views ? (uint32_t)view : kViewNone};
     HIP_TRY(launch_first_hit(p, tail, s));
-    HIP_TRY(hipEventRecord(d->done, s));
-    d->done_stream = s;
+    HIP_TRY(d->done.record(s));
     if (host_out) {
         HIP_TRY(hipMemcpyAsync(host_out, out, words * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));

@@ -552,8 +552,7 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
         HIP_TRY(hipMemsetAsync(d->counter.get(), 0, parts * 128, s));
         HIP_TRY(launch_recorded(d, resolve_trace_variant(p, f.want), p, TraceTail{}, (uint32_t)blocks, s));
     }
-    HIP_TRY(hipEventRecord(d->done, s));
-    d->done_stream = s;
+    HIP_TRY(d->done.record(s));
     d->last_jobs = 0;  // the slab holds counts now, not samples
     return 0;
 }
@@ -626,7 +625,7 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
         AccumState &acc = *ap->acc;
         // the sums are the accumulator's own, not the device's scratch: a pass on
         // another stream than the last one waits for it here
-        if (acc.done_stream && acc.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, acc.done, 0));
+        HIP_TRY(acc.done.wait(s));
         // the first pass (after creation or a reset) starts every fold from 0.0f
         if (ap->n0 == 0) HIP_TRY(hipMemsetAsync(acc.sums.get(), 0, 3 * width * height * sizeof(float), s));
         tail.sums = acc.sums.get(), tail.n0 = ap->n0, tail.stride = acc.stride;
@@ -657,14 +656,11 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
     uint32_t &nslab = done.nslab;  // (counted frames: event triple per launch)
     for (size_t r0 = row_lo; r0 < row_hi; r0 += units_per_slab, ++nslab) {
         const size_t rows = std::min(units_per_slab, row_hi - r0);
-        hipEvent_t *ev3 = nullptr;
+        DevEvent *ev3 = nullptr;
         if (timed) {
-            while (d->tev.size() < 3 * (size_t)(nslab + 1)) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreate(&e));
-                d->tev.push_back(e);
-            }
+            if (d->tev.size() < 3 * (size_t)(nslab + 1)) d->tev.resize(3 * (size_t)(nslab + 1));
             ev3 = &d->tev[3 * (size_t)nslab];
+            for (int k = 0; k < 3; ++k) HIP_TRY(ev3[k].create(true));
         }
         const uint64_t njobs = rows * jobs_per_unit;
         p.slab_row0 = adapt ? 0u : (uint32_t)r0;
@@ -675,7 +671,7 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
         if (ap) p.gj32 = (uint64_t)width * height * ap->acc->stride < (1ull << 32) ? 1u : 0u;
         p.njobs = (uint32_t)njobs;
         p.npix = adapt ? (uint32_t)rows : (uint32_t)(rows * width);
-        if (timed) HIP_TRY(hipEventRecord(ev3[0], s));
+        if (timed) HIP_TRY(hipEventRecord(ev3[0].get(), s));
         if (njobs) {
             const LaunchPlan lp = plan_launch(d, p, f, f.tv, njobs);
             const uint64_t blocks = lp.blocks, nwaves = lp.nwaves, chunk = lp.chunk, parts = lp.parts;
@@ -717,18 +713,14 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             ++done.launches;
             done.waves = (uint32_t)nwaves;
         }
-        if (timed) HIP_TRY(hipEventRecord(ev3[1], s));
+        if (timed) HIP_TRY(hipEventRecord(ev3[1].get(), s));
         if (!fused)  // (spp 0: no samples, the resolve still writes every pixel)
             HIP_TRY(launch_resolve_ex(d->samples.get(), d_out, (uint32_t)(rows * width), spp, f.inv_spp,
                                       (uint32_t)width, (uint32_t)r0, s));
-        if (timed) HIP_TRY(hipEventRecord(ev3[2], s));
+        if (timed) HIP_TRY(hipEventRecord(ev3[2].get(), s));
     }
-    HIP_TRY(hipEventRecord(d->done, s));
-    d->done_stream = s;
-    if (ap) {
-        HIP_TRY(hipEventRecord(ap->acc->done, s));
-        ap->acc->done_stream = s;
-    }
+    HIP_TRY(d->done.record(s));
+    if (ap) HIP_TRY(ap->acc->done.record(s));
     return 0;
 }
 
@@ -803,10 +795,10 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     DeviceState *d = nullptr;
     rc = device_for(w, o.device, d);
     if (rc) return rc;
-    hipStream_t s = stream ? stream : d->stream;
+    hipStream_t s = stream ? stream : d->stream.get();
     // the device's scratch (job counters, rings, slab, stats) is shared by every
     // frame on it: a frame enqueued on another stream waits for the last one
-    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
+    HIP_TRY(d->done.wait(s));
 
     rc = plan_sample_storage(d, o, width, height, sp, d_replay, ap, s, f);
     if (rc) return rc;
@@ -852,8 +844,8 @@ int collect_frame_stats(DeviceState *d, RtRenderStats *stats) {
     double trace_ms = 0.0, resolve_ms = 0.0;
     for (uint32_t k = 0; k < pd.nslab; ++k) {
         float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, d->tev[3 * k], d->tev[3 * k + 1]));
-        HIP_TRY(hipEventElapsedTime(&b, d->tev[3 * k + 1], d->tev[3 * k + 2]));
+        HIP_TRY(hipEventElapsedTime(&a, d->tev[3 * k].get(), d->tev[3 * k + 1].get()));
+        HIP_TRY(hipEventElapsedTime(&b, d->tev[3 * k + 1].get(), d->tev[3 * k + 2].get()));
         trace_ms += a;
         resolve_ms += b;
     }
@@ -1016,12 +1008,12 @@ int render_frame_host(WorldState &w, const CameraModel &cam, size_t width, size_
         rc = device_for(w, devs[0], root);
         if (rc) return rc;
         HIP_TRY(root->out.grow(width * height));
-        rc = render_frame_multi(w, cam, width, height, o, root->out.get(), root->stream, stats);
+        hipStream_t s = root->stream.get();
+        rc = render_frame_multi(w, cam, width, height, o, root->out.get(), s, stats);
         if (rc) return rc;
         HIP_TRY(hipSetDevice(devs[0]));
-        HIP_TRY(hipMemcpyAsync(host_out, root->out.get(), width * height * 4, hipMemcpyDeviceToHost,
-                               root->stream));
-        HIP_TRY(hipStreamSynchronize(root->stream));
+        HIP_TRY(hipMemcpyAsync(host_out, root->out.get(), width * height * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         return 0;
     }
     const uint32_t nranks = o.nranks ? o.nranks : 1;
@@ -1036,10 +1028,11 @@ int render_frame_host(WorldState &w, const CameraModel &cam, size_t width, size_
     int rc = device_for(w, o.device, d);
     if (rc) return rc;
     HIP_TRY(d->out.grow(T * width));
-    rc = render_frame(w, cam, width, height, o, d->out.get(), d->stream, stats);
+    hipStream_t s = d->stream.get();
+    rc = render_frame(w, cam, width, height, o, d->out.get(), s, stats);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(host_out, d->out.get(), T * width * 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemcpyAsync(host_out, d->out.get(), T * width * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
 }  // namespace rtamd

@@ -16,11 +16,6 @@ namespace rtamd {
 
 namespace {
 
-int fail(const char *who, const std::string &msg) {
-    set_error(std::string(who) + ": " + msg);
-    return -1;
-}
-
 // a x b as maths.rs:88-94: each product rounded, then the subtraction
 void cross(const float a[3], const float b[3], float out[3]) {
     out[0] = a[1] * b[2] - a[2] * b[1];
@@ -66,9 +61,9 @@ int history_enable(AccumState &a, const CameraModel &cam, bool on, float max_his
         return 0;
     }
     // (the last resolve may still use the buffers)
-    if (a.device >= 0 && a.done_stream) {
+    if (a.device >= 0 && a.done.recorded()) {
         HIP_TRY(hipSetDevice(a.device));
-        HIP_TRY(hipEventSynchronize(a.done));
+        HIP_TRY(a.done.sync());
     }
     for (auto &h : a.hist) {
         h.col.reset();
@@ -107,35 +102,19 @@ int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOption
     if (rc) return rc;
     RtFilterOptions fo{};
     if (filter) fo = *filter;
-    if ((uint64_t)a.width * a.height >= (1ull << 31))
-        return fail(who, "the accumulator's frame has 2^31 pixels or more: a history takes width * height below "
-                         "2^31 (an accumulator up to 2^32 - 1)");
-
-    std::unique_lock<std::recursive_mutex> lock;
-    WorldState *wp = accum_begin(a, *cam, lock);
-    if (!wp) return fail(who, "the accumulator's world was freed");
-    WorldState &w = *wp;
-    if (!a.hist_enabled) return fail(who, "the accumulator's history is not enabled (rt_history_enable)");
-    if (a.held == 0) return fail(who, "no samples held");
-    DeviceState *d = nullptr;
-    rc = device_for(w, a.device, d);
+    AccumRead r{a, *cam, who, out_rgb, out_rgba, on_device};
+    rc = r.lock_world("a history");
     if (rc) return rc;
-    hipStream_t s = stream ? stream : d->stream;
+    if (!a.hist_enabled) return fail(who, "the accumulator's history is not enabled (rt_history_enable)");
+    rc = r.begin(stream);
+    if (rc) return rc;
+    hipStream_t s = r.s;
     const size_t npix = a.width * a.height;
-    FilterState &f = accum_filter(a);
-    std::lock_guard<std::mutex> flock(f.mu);
     for (auto &h : a.hist) {
         HIP_TRY(h.col.grow(npix));
         HIP_TRY(h.guide.grow(npix));
     }
     if (filter) HIP_TRY(a.hist_rgb.grow(3 * npix));
-    if (!f.done) HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
-    // as filter_accum: d->done is recorded again below, on s ...
-    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
-    // ... after the accumulator's last pass and its last resolve (the snapshots) ...
-    if (a.done_stream && a.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, a.done, 0));
-    // ... and after the filter's last run (its staging is written below)
-    if (f.done_stream && f.done_stream != s) HIP_TRY(hipStreamWaitEvent(s, f.done, 0));
 
     // a snapshot of another scene: both go; a cur of another camera becomes prev.
     // Under a clamp that keeps history over edits (only materials can be edited:
@@ -150,15 +129,6 @@ int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOption
     // (valid again once the kernel that fills it is enqueued)
     cur.valid = false;
 
-    rc = accum_records(a, w, *cam, f, s, who);
-    if (rc) return rc;
-
-    float *d_rgb = out_rgb;
-    uint32_t *d_rgba = static_cast<uint32_t *>(out_rgba);
-    if (!on_device) {
-        rc = filter_stage_outputs(f, out_rgb, out_rgba, d_rgb, d_rgba);
-        if (rc) return rc;
-    }
     HistoryResolve k{};
     k.sums = a.sums.get();
     k.plane = npix;
@@ -174,8 +144,8 @@ int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOption
     k.sigma_z = a.hist_sigma_z;
     k.cur_col = cur.col.get();
     k.cur_guide = cur.guide.get();
-    k.out_rgb = filter ? a.hist_rgb.get() : d_rgb;
-    k.out_rgba = filter ? nullptr : d_rgba;
+    k.out_rgb = filter ? a.hist_rgb.get() : r.d_rgb;
+    k.out_rgba = filter ? nullptr : r.d_rgba;
     k.width = (uint32_t)a.width;
     k.height = (uint32_t)a.height;
     const HistoryClamp clamp{a.clamp_gamma, a.clamp_radius, nullptr};
@@ -188,18 +158,13 @@ int history_resolve(AccumState *ap, const CameraModel *cam, const RtFilterOption
         FilterPack src{};
         src.rgb = a.hist_rgb.get();
         src.records = k.records;
-        rc = filter_enqueue(f, fo, src, d_rgb, d_rgba, s);
+        rc = filter_enqueue(*r.f, fo, src, r.d_rgb, r.d_rgba, s);
         if (rc) return rc;
     } else {
-        HIP_TRY(hipEventRecord(f.done, s));
-        f.done_stream = s;
+        // (host outputs went to the filter's staging: its next run, on another stream, waits)
+        HIP_TRY(r.f->done.record(s));
     }
-    // the next pass, on whatever stream, writes the sums after this run read them
-    HIP_TRY(hipEventRecord(d->done, s));
-    d->done_stream = s;
-    HIP_TRY(hipEventRecord(a.done, s));
-    a.done_stream = s;
-    return on_device ? 0 : filter_fetch_outputs(f, out_rgb, out_rgba, s);
+    return r.finish();
 }
 
 int history_read_length(AccumState &a, const CameraModel &cam, float *len) {
@@ -214,7 +179,7 @@ int history_read_length(AccumState &a, const CameraModel &cam, float *len) {
         return 0;
     }
     HIP_TRY(hipSetDevice(a.device));
-    HIP_TRY(hipEventSynchronize(a.done));
+    HIP_TRY(a.done.sync());
     std::vector<float4> col(npix);
     HIP_TRY(hipMemcpy(col.data(), cur.col.get(), npix * sizeof(float4), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < npix; ++i) len[i] = col[i].w;
@@ -225,16 +190,9 @@ int history_run(size_t width, size_t height, float max_history, float sigma_z, c
                 const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
                 const void *records, float *out_rgbl, int device, const RtClampOptions *clamp, float *out_box) {
     // (the arguments were checked by rt_history_run or rt_clamp_run)
-    const char *who = clamp ? "rt_clamp_run" : "rt_history_run";
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_error(std::string(who) + ": no HIP device available: the MI355X render path requires a GPU");
-        return -3;
-    }
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    if (dev >= count) return fail(who, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(dev));
+    int dev = -1;
+    const int rc = select_device(device, dev, clamp ? "rt_clamp_run" : "rt_history_run");
+    if (rc) return rc;
     const size_t npix = width * height;
     DevBuf<float> d_rgb;
     DevBuf<uint32_t> d_n, d_rec;

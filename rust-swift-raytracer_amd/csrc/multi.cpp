@@ -84,7 +84,7 @@ int render_frame_multi(WorldState &w, const CameraModel &cam, size_t width, size
     for (uint32_t g = 0; g < n; ++g) {
         rc = device_for(w, devs[g], ds[g]);
         if (rc) return rc;
-        ss[g] = (g == 0 && stream) ? stream : ds[g]->stream;
+        ss[g] = (g == 0 && stream) ? stream : ds[g]->stream.get();
         if (n > 1) HIP_TRY(ds[g]->tile.grow(max_rows * width));
     }
     if (n > 1) {
@@ -165,8 +165,7 @@ int render_frame_multi(WorldState &w, const CameraModel &cam, size_t width, size
     // the tiles and the gather buffer are reused by the next frame on these streams
     for (uint32_t g = 0; g < n; ++g) {
         HIP_TRY(hipSetDevice(devs[g]));
-        HIP_TRY(hipEventRecord(ds[g]->done, ss[g]));
-        ds[g]->done_stream = ss[g];
+        HIP_TRY(ds[g]->done.record(ss[g]));
     }
     // the counted tiles' counters, collected only now: every device's tile, the
     // gather and the assembly are enqueued before the host waits on any of them
@@ -206,10 +205,10 @@ int render_frame_multi(WorldState &w, const CameraModel &cam, size_t width, size
             stats->serial_checked = sst.serial_checked;
             stats->serial_chain_breaks = sst.serial_chain_breaks;
             float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, ds[0]->sev[0], ds[0]->sev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms, ds[0]->sev[0].get(), ds[0]->sev[1].get()));
             stats->serial_ms = ms;
             if (width * height * (size_t)std::max(o.samples_per_pixel, 0) > 0) {
-                HIP_TRY(hipEventElapsedTime(&ms, ds[0]->sev[0], ds[0]->sev[2]));
+                HIP_TRY(hipEventElapsedTime(&ms, ds[0]->sev[0].get(), ds[0]->sev[2].get()));
                 stats->serial_setup_ms = ms;
             }
         }

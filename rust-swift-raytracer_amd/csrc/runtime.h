@@ -14,6 +14,7 @@
 
 #include "bvh.h"
 #include "device_buffer.h"
+#include "device_fence.h"
 #include "render.h"
 #include "scene.h"
 
@@ -40,13 +41,12 @@ const std::string &last_error();
 // One device's copy of a scene plus the scratch a frame needs.  Buffers grow
 // on demand and persist across frames (the interactive flow re-renders the
 // same scene with a moved camera, GameView.swift:198-219 / lib.rs:60-63).
-// Every buffer owns its memory (device_buffer.h): the destructor selects the
-// device and destroys the events and the stream, the buffers follow as members.
+// Every member owns what it holds (device_buffer.h, device_fence.h): the
+// destructor selects the device, the members follow.
 struct DeviceState {
     int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t sev[3] = {nullptr, nullptr, nullptr};  // SERIAL mode: start, tables done, states found
+    DevStream stream;
+    DevEvent sev[3];  // SERIAL mode: start, tables done, states found
     DevBuf<float4> sph_hot, sph_cold, tri_hot, tri_geo;
     DevBuf<float> mats;
     DevBuf<float4> sph_shade;
@@ -131,8 +131,7 @@ struct DeviceState {
     DevBuf<uint32_t> tile;                                      // multi-device: this rank's tile
     DevBuf<uint32_t> gath;                                      // multi-device root: gathered tiles
     DevBuf<uint32_t> first_hit;                                 // first-hit records / views (host path)
-    hipEvent_t done = nullptr;       // end of the last frame enqueued on this device ...
-    hipStream_t done_stream = nullptr;  // ... and the stream it was enqueued on
+    Fence done;                      // the last work enqueued on the scratch and the scene arrays
     DevBuf<uint32_t> replay;
     // SERIAL mode (render_frame_serial): start states, candidate offsets, the
     // stream window of a chunk, xorshift jump matrices, control block
@@ -178,7 +177,7 @@ struct DeviceState {
     // end) and its wave records copied to pinned host memory; with
     // render_frame(..., defer_stats) the host collects them later
     // (collect_frame_stats), so several devices' counted frames run at once
-    std::vector<hipEvent_t> tev;
+    std::vector<DevEvent> tev;
     PinnedBuf<unsigned long long> hrec;
     struct PendingStats {
         bool active = false;
@@ -254,9 +253,8 @@ struct FilterState {
     DevBuf<float4> g0, g1;        // {normal, prim bits}, {position, sigma_z * t}
     DevBuf<float> in_rgb, out_rgb;        // host entries: staging
     DevBuf<uint32_t> in_rec, out_rgba;
-    hipStream_t stream = nullptr; // its own (rt_filter_run; rt_filter_run_device with a null stream)
-    hipEvent_t done = nullptr;    // end of the last run enqueued ...
-    hipStream_t done_stream = nullptr;  // ... and its stream: a run on another waits for it
+    DevStream stream;             // its own (rt_filter_run; rt_filter_run_device with a null stream)
+    Fence done;                   // the last run enqueued on the scratch and the staging
     std::mutex mu;                // one run at a time per filter
     ~FilterState();
 };
@@ -276,8 +274,7 @@ struct AccumState {
     uint64_t edit_version = 0;    // ... and the scene version
     DevBuf<float> sums;           // 3 planes of width * height (R, G, B), top row first
     DevBuf<uint32_t> replay;      // REPLAY: width * height * stride start states
-    hipEvent_t done = nullptr;    // end of the last pass ...
-    hipStream_t done_stream = nullptr;  // ... and the stream it ran on (nullptr: none yet)
+    Fence done;                   // the last pass or read enqueued on the sums, adaptive planes and snapshots
     // Adaptive accumulation (rt_adapt_enable): the pixels still
     // sampled are those of list[cur] (frame indices, ascending), nactive of
     // them, all holding `held` samples; the others stopped at count[pixel].

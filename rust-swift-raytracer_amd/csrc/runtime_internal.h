@@ -1,6 +1,6 @@
 // runtime_internal.h -- what the host runtime's units share with each other
-// (device_state, primary_lists, frame, serial_states, multi, accum) and with
-// nobody else: runtime.h is the interface the C ABI sees.
+// (device_state, primary_lists, frame, serial_states, multi, accum) and, of
+// this, the argument checks with the C ABI, whose interface is runtime.h.
 #pragma once
 
 #include <cstdlib>
@@ -44,13 +44,34 @@ inline bool same_cam(const CameraModel &a, const CameraModel &b) {
     return std::memcmp(&a, &b, sizeof(a)) == 0;
 }
 
+// ---- checks, shared with the C ABI: every message reads "<who>: <msg>"
+inline int fail(const char *who, const std::string &msg) {
+    set_error(std::string(who) + ": " + msg);
+    return -1;
+}
+
+// a size the filter, the history and the first-hit records take (noun: "image size", "frame size")
+inline int check_image_size(size_t width, size_t height, const char *noun, const char *who) {
+    if (width == 0 || height == 0 || (uint64_t)width >= (1ull << 31) || (uint64_t)height >= (1ull << 31) ||
+        (uint64_t)width * height >= (1ull << 31))
+        return fail(who, std::string(noun) + ": width and height at least 1, width * height below 2^31");
+    return 0;
+}
+
+// v is finite and at least lo (above: more than lo); false for a NaN
+inline bool finite_from(float v, float lo, bool above = false) {
+    return (above ? v > lo : v >= lo) && v <= 3.4028234663852886e38f;
+}
+
 static_assert(kPrimaryTriStripW == kTriStripW, "render.h and bvh.h strip widths");
 static constexpr uint64_t kMaxParts = kMaxJobParts;  // job-queue partitions (render.h)
 static constexpr uint32_t kPixtabParts = 64;  // the pixel table pass's (zeroed by the window kernel)
 
-// device_state.cpp: w's state on device `want` (< 0: the current device),
-// created on first use -- stream and events, the scene upload, the LDS layout
-// and occupancy decisions.  Selects the device.
+// device_state.cpp: device `want` (< 0: the current one) counted, range-checked
+// and selected -> dev (who: a prefix for the messages, none for null)
+int select_device(int want, int &dev, const char *who = nullptr);
+// ... and w's state on it, created on first use -- stream and events, the
+// scene upload, the LDS layout and occupancy decisions
 int device_for(WorldState &w, int want, DeviceState *&out);
 
 // frame.cpp: the parts of a TraceParams that do not depend on the kind of
@@ -103,6 +124,32 @@ int filter_enqueue(FilterState &f, const RtFilterOptions &o, FilterPack src, flo
 // ... and device staging of the host outputs asked for, with their copies back (waits)
 int filter_stage_outputs(FilterState &f, float *out_rgb, void *out_rgba, float *&d_rgb, uint32_t *&d_rgba);
 int filter_fetch_outputs(FilterState &f, float *out_rgb, void *out_rgba, hipStream_t s);
+// A call that reads an accumulator's held samples on a stream (filter_accum,
+// history_resolve; the outputs are device memory if on_device, else host).
+// lock_world: the frame's size (taker: who takes no more, for the message), the
+// world locked, the reset rule.  begin: samples held, the device, s, the filter
+// locked, s behind the three fences, the records current, d_rgb / d_rgba where
+// the kernels write.  finish: the device's and the accumulator's fences
+// recorded, host outputs fetched.
+struct AccumRead {
+    AccumState &a;
+    const CameraModel &cam;
+    const char *who;
+    float *out_rgb;
+    void *out_rgba;
+    bool on_device;
+    WorldState *w = nullptr;
+    DeviceState *d = nullptr;
+    hipStream_t s = nullptr;
+    FilterState *f = nullptr;
+    std::unique_lock<std::recursive_mutex> lock;
+    std::unique_lock<std::mutex> flock;
+    float *d_rgb = nullptr;
+    uint32_t *d_rgba = nullptr;
+    int lock_world(const char *taker);
+    int begin(hipStream_t stream);
+    int finish();
+};
 
 // multi.cpp: devices [first, first + n) (first < 0: from the current device), checked
 int device_list(int first, int n, std::vector<int> &devs);

@@ -96,8 +96,8 @@ int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size
     const uint64_t N = (uint64_t)width * height * spp;
     const uint32_t depth = (uint32_t)std::max(o.max_ray_bounces, 0);
     int rc = 0;
-    if (d->done_stream && d->done_stream != s) HIP_TRY(hipStreamWaitEvent(s, d->done, 0));
-    HIP_TRY(hipEventRecord(d->sev[0], s));
+    HIP_TRY(d->done.wait(s));
+    HIP_TRY(hipEventRecord(d->sev[0].get(), s));
     HIP_TRY(d->sstates.grow(std::max<uint64_t>(N, 1)));
     RtRenderOptions ob = o;
     // the inner passes read and write d's buffers (d->samples, d->stab, ...):
@@ -215,7 +215,7 @@ int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size
         for (;;) {
             HIP_TRY(launch_serial_tables(d->stab.get(), d->sscan.get(), (uint32_t)npix, (uint32_t)spp, (uint32_t)L,
                                          (uint32_t)n0, s));
-            HIP_TRY(hipEventRecord(d->sev[2], s));
+            HIP_TRY(hipEventRecord(d->sev[2].get(), s));
             HIP_TRY(hipMemcpyAsync(sm, sums, sizeof(sm), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if (sm[3] != 0.0) {
@@ -336,17 +336,11 @@ int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size
         // those queued past the end exit at once (ctrl[0])
         uint32_t ctrl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         double t_enqueue = 0, t_wait = 0;  // (RT_AMD_SERIAL_DEBUG)
-        struct DebugEvents {  // (destroyed on every way out)
-            hipEvent_t e[2] = {nullptr, nullptr};
-            ~DebugEvents() {
-                for (hipEvent_t x : e)
-                    if (x) (void)hipEventDestroy(x);
-            }
-        } dbg_ev;
+        DevEvent dbg_ev[2];
         DevBuf<unsigned long long> dbg_cnt;  // (coalescing search counters)
         if (env_u64("RT_AMD_SERIAL_DEBUG", 0)) {
-            for (auto &e : dbg_ev.e) HIP_TRY(hipEventCreate(&e));
-            HIP_TRY(hipEventRecord(dbg_ev.e[0], s));
+            for (auto &e : dbg_ev) HIP_TRY(e.create(true));
+            HIP_TRY(hipEventRecord(dbg_ev[0].get(), s));
             HIP_TRY(dbg_cnt.grow(4));
             HIP_TRY(hipMemsetAsync(dbg_cnt.get(), 0, 4 * 8, s));
         }
@@ -423,12 +417,12 @@ int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size
             stats->serial_iterations = ctrl[3];
         }
         final_state = ctrl[1];
-        if (dbg_ev.e[0]) {
-            HIP_TRY(hipEventRecord(dbg_ev.e[1], s));
-            HIP_TRY(hipEventSynchronize(dbg_ev.e[1]));
+        if (dbg_ev[0]) {
+            HIP_TRY(hipEventRecord(dbg_ev[1].get(), s));
+            HIP_TRY(hipEventSynchronize(dbg_ev[1].get()));
             float a = 0, b = 0;
-            HIP_TRY(hipEventElapsedTime(&a, d->sev[0], dbg_ev.e[0]));
-            HIP_TRY(hipEventElapsedTime(&b, dbg_ev.e[0], dbg_ev.e[1]));
+            HIP_TRY(hipEventElapsedTime(&a, d->sev[0].get(), dbg_ev[0].get()));
+            HIP_TRY(hipEventElapsedTime(&b, dbg_ev[0].get(), dbg_ev[1].get()));
             std::fprintf(stderr, "serial debug: GPU estimate + tables %.1f ms, iterations %.1f ms\n", a, b);
             unsigned long long c[4] = {0, 0, 0, 0};
             HIP_TRY(hipMemcpy(c, dbg_cnt.get(), sizeof(c), hipMemcpyDeviceToHost));
@@ -468,7 +462,7 @@ int serial_find_states(WorldState &w, const CameraModel &cam, size_t width, size
                          ctrl[3], ctrl[6], (unsigned long long)queued, t_prep, t_enqueue, t_wait);
         }
     }
-    HIP_TRY(hipEventRecord(d->sev[1], s));
+    HIP_TRY(hipEventRecord(d->sev[1].get(), s));
     if (N > 0 && (o.flags & RT_FLAG_SERIAL_CHECK)) {
         // the chain the reference's one stream forms (common.rs:321-341):
         // sample 0 starts at the seed, sample j ends where j + 1 starts,
@@ -529,7 +523,7 @@ int render_frame_serial(WorldState &w, const CameraModel &cam, size_t width, siz
     DeviceState *d = nullptr;
     rc = device_for(w, o.device, d);
     if (rc) return rc;
-    hipStream_t s = stream ? stream : d->stream;
+    hipStream_t s = stream ? stream : d->stream.get();
     rc = serial_find_states(w, cam, width, height, o, d, s, stats);
     if (rc) return rc;
     const uint64_t N = (uint64_t)width * height * (uint64_t)std::max(o.samples_per_pixel, 0);
@@ -547,11 +541,11 @@ int render_frame_serial(WorldState &w, const CameraModel &cam, size_t width, siz
         stats->serial_checked = keep.serial_checked;
         stats->serial_chain_breaks = keep.serial_chain_breaks;
         float ms = 0.0f;
-        HIP_TRY(hipEventSynchronize(d->sev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, d->sev[0], d->sev[1]));
+        HIP_TRY(hipEventSynchronize(d->sev[1].get()));
+        HIP_TRY(hipEventElapsedTime(&ms, d->sev[0].get(), d->sev[1].get()));
         stats->serial_ms = ms;
         if (N > 0) {
-            HIP_TRY(hipEventElapsedTime(&ms, d->sev[0], d->sev[2]));
+            HIP_TRY(hipEventElapsedTime(&ms, d->sev[0].get(), d->sev[2].get()));
             stats->serial_setup_ms = ms;
         }
     }

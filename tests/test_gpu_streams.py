@@ -32,21 +32,24 @@ trace time after the pair began; where the later frame runs on it, a third
 light frame on a user stream, which waits for the library's stream in turn,
 carries the event.
 
-Which wait or lock each case goes through (csrc/):
+Which wait or lock each case goes through (csrc/; the three fences, device_fence.h
+and DESIGN.md 4, "Stream ordering": d->done the device's, a.done / acc.done the accumulator's, f.done
+the filter's; a wait is fence.wait(stream), the host's wait fence.sync()):
   (a) frame after frame            frame.cpp render_frame: the device's scratch (d->done)
   (b) the slab path                the same wait; d->samples and the resolve kernel
   (c) REPLAY after COUNTER         the same wait before the pass's launches; an
                                    accumulator owns its table, so d->replay's upload is
                                    reached only by the "frame" variant (rt_render_device)
   (d) an accumulator on three      frame.cpp enqueue_launches (acc.done before a pass),
-      streams, then a filter       filter.cpp filter_accum (a.done before the filter reads
-                                   the sums), first_hit.cpp (d->done before the records),
-                                   filter.cpp enqueue (f.done: the second filter run, on
-                                   another stream), accum.cpp accum_read (the host waits)
-      filter between frames        filter.cpp filter_accum (d->done before the filter records it
-                                   again on its own stream)
+      streams, then a filter       filter.cpp AccumRead::begin, for filter_accum (a.done before
+                                   the filter reads the sums; f.done: the second filter run, on
+                                   another stream), first_hit.cpp (d->done before the records),
+                                   filter.cpp filter_enqueue (f.done again, a stand-alone run's
+                                   only wait), accum.cpp accum_read (the host waits)
+      filter between frames        AccumRead::begin (d->done before finish records it
+                                   again on the filter's stream)
       adaptive                     accum.cpp accum_add (a.done before the frame's copy of
-                                   a pass that traced nothing); filter_accum's wait before
+                                   a pass that traced nothing); accum_records' wait before
                                    new records (f.done) after a reset
   (e) first-hit between frames     first_hit.cpp and frame.cpp, both directions
   (f) two worlds                   no wait: nothing is shared
@@ -57,7 +60,10 @@ Which wait or lock each case goes through (csrc/):
   (i) a stand-alone filter         filter.cpp filter_run (f.done before the host entry's staging
                                    copies) and RtFilter::mu; the host entry waits, so the
                                    witness is as in (h)
-Every hipStreamWaitEvent of frame.cpp, accum.cpp, filter.cpp, first_hit.cpp and
+  (j) history resolves on two      AccumRead::begin, for history.cpp history_resolve (a.done: the
+      streams behind a pass        pass, then the first resolve's snapshots; f.done: the first
+                                   resolve's staging; d->done), history_read_length (the host waits)
+Every wait on a fence in frame.cpp, accum.cpp, filter.cpp, first_hit.cpp, history.cpp and
 serial_states.cpp is reached by a case.  Stream capture has no test (graph replay
 is left to a change of its own).
 """
@@ -67,7 +73,9 @@ import os
 import numpy as np
 import pytest
 
+import clamp_ref as CR
 import filter_ref as FR
+import history_ref as HR
 import oracle as O
 import raytracer_amd as R
 import scenes as S
@@ -76,6 +84,7 @@ import test_gpu_first_hit as FH
 from conftest import scene_text
 from test_gpu_accum import Expect, assert_sums_equal
 from test_gpu_filter import assert_same, synthetic
+from test_gpu_history import same_bits
 from test_gpu_parity import assert_bits_equal, oracle_samples_to_gpu_order
 
 pytestmark = pytest.mark.gpu
@@ -650,4 +659,82 @@ def test_g_material_edits_with_frames_in_flight(name):
     assert_bits_equal(as_frame(outs[0], w, h), want[0], f"{name}: frame 0 against its solo render")
     for k in range(1, len(want)):
         assert_bits_equal(as_frame(outs[k], w, h), want[k], f"{name}: frame {k} against the oracle with {k} edits")
+    world.close()
+
+
+# ---- (j) history resolves behind an accumulator's pass --------------------------------------------------
+
+@pytest.mark.parametrize("clamp", [None, dict(gamma=1.0, radius=2)], ids=["plain", "clamp"])
+def test_j_history_resolves_behind_a_running_pass(clamp):
+    """The set-up resolves 3 samples of a camera moved aside, so the history holds that
+    view.  Then, back at the scene's camera and behind a heavy frame on sA: add(2) on sA,
+    the resolve on sB, a second, filtered resolve on sC (it reads the prev the first one
+    made of the set-up's view, rewrites the same cur and runs the filter behind the first
+    one's use of its staging), and rt_history_read_length at once, which waits by itself."""
+    torch, (sA, sB, sC) = gpu(3)
+    w, h, stride = 96, 64, 8
+    hw, hh = A_W, A_H
+    want_heavy, _ = solo("rtow", hw, hh, A_SPP, A_DEPTH)
+    world = R.World(source("rtow"))
+    cam0 = world.camera()
+    world.translate_camera(0.02, 0.0, 0.0)
+    cam_p = world.camera()
+
+    def expect():
+        moved = O.Scene(source("rtow"))
+        moved.set_camera(cam_p)
+        sums_p = Expect(moved, w, h, stride, 8).sums(3)
+        rec_p = world.first_hit(w, h, device=0)  # (pinned by test_gpu_first_hit.py)
+        world.set_camera(cam0)
+        rec = world.first_hit(w, h, device=0)
+        world.set_camera(cam_p)
+        ref = HR.History() if clamp is None else CR.ClampHistory(clamp=clamp)
+        ref.resolve(sums_p, np.full((h, w), 3, np.uint32), rec_p, cam_p, 0)
+        rgb, px, length = ref.resolve(exp.sums(2), np.full((h, w), 2, np.uint32), rec, cam0, 0)
+        assert (length > 2).any(), "no pixel takes history: the resolves would not read prev"
+        return rgb, px, length, FR.filter_image(rgb, rec)
+
+    exp = memo("d expect", lambda: Expect(O.Scene(source("rtow")), w, h, stride, 8))
+    want_rgb, want_px, want_len, want_filtered = memo(("j expect", str(clamp)), expect)
+    out_heavy = frame_buf(torch, hw, hh)
+    out_2, px_1, px_2 = (frame_buf(torch, w, h) for _ in range(3))
+    rgb_1, rgb_2 = (torch.zeros(h * w * 3, dtype=torch.float32, device="cuda") for _ in range(2))
+    acc = world.accumulator(w, h, stride, device=0)
+    acc.history_enable()
+    if clamp is not None:
+        acc.clamp_enable(**clamp)
+    acc.add_device(3, out_2.data_ptr(), sB.cuda_stream)  # (the moved camera's view; every kernel and buffer)
+    acc.resolved_device(rgb_2.data_ptr(), px_2.data_ptr(), sC.cuda_stream, filter={})
+    acc.resolved_device(rgb_1.data_ptr(), px_1.data_ptr(), sB.cuda_stream)
+    world.set_camera(cam0)
+    enqueue(world, hw, hh, out_heavy, sA.cuda_stream, **B)
+    torch.cuda.synchronize()
+    for t in (out_heavy, out_2, px_1, px_2, rgb_1, rgb_2):
+        t.zero_()
+    torch.cuda.synchronize()
+
+    enqueue(world, hw, hh, out_heavy, sA.cuda_stream, A_SPP, A_DEPTH)
+    assert acc.add_device(2, out_2.data_ptr(), sA.cuda_stream) is None
+    e1 = mark(torch, sA)
+    acc.resolved_device(rgb_1.data_ptr(), px_1.data_ptr(), sB.cuda_stream)
+    e2 = mark(torch, sB)
+    acc.resolved_device(rgb_2.data_ptr(), px_2.data_ptr(), sC.cuda_stream, filter={})
+    e3 = mark(torch, sC)
+    running = not e1.query()
+    length = acc.history_length()  # (no synchronise before it)
+    held = acc.samples
+    torch.cuda.synchronize()
+
+    what = f"history resolves on two streams ({'clamp' if clamp else 'plain'})"
+    assert_in_flight(running, what)
+    assert_ordered([("add(2)", e1), ("the resolve", e2), ("the filtered resolve", e3)], what)
+    assert held == 2
+    same_bits(length, want_len, f"{what}: history_length read with no wait before")
+    assert_bits_equal(as_frame(out_heavy, hw, hh), want_heavy, f"{what}: the heavy frame against its solo render")
+    assert_bits_equal(as_frame(out_2, w, h), exp.frame(2), f"{what}: frame after add(2)")
+    same_bits(rgb_1.cpu().numpy().reshape(h, w, 3), want_rgb, f"{what}: the resolve on sB, out_rgb")
+    assert as_frame(px_1, w, h).tobytes() == want_px.tobytes(), f"{what}: the resolve on sB, RGBA8"
+    got = (rgb_2.cpu().numpy().reshape(h, w, 3), as_frame(px_2, w, h))
+    assert_same(got, want_filtered, f"{what}: the filtered resolve on sC")
+    acc.close()
     world.close()
