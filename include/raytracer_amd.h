@@ -163,7 +163,9 @@ int rt_render_ex(Rust_CFramebuffer framebuffer, const Rust_WorldHandle *handle,
 /* Threading: one frame at a time per handle.  Calls from several host threads
  * on one handle are serialised by a lock; frames enqueued on different streams
  * of one device are ordered (the later waits for the earlier: they share the
- * device's scratch). */
+ * device's scratch).  Inside a frame the library may run part of it on a
+ * stream of its own, which starts behind what the frame's stream holds and
+ * which that stream waits for before the call returns. */
 
 /* Same, but the tile is written to DEVICE memory `d_rgba` (rt_tile_rows*width
  * RGBA8; with ndevices >= 1 the whole width*height frame on the first device)
@@ -726,6 +728,13 @@ int rt_trace_plain(const Rust_WorldHandle *handle, int device);
  * every row was traced.  Both give bit-identical frames.
  * Negative: an error. */
 int rt_sky_rows(const Rust_WorldHandle *handle, int device);
+
+/* Diagnostics: 1 when the last frame launch on `device` (-1 = current) ran its
+ * sky kernel on the library's side stream, beside the trace launches, 0 when
+ * it ran on the frame's stream in front of them or the frame had no sky kernel
+ * (no sky rows, nothing but sky rows, a capturing stream, RT_AMD_SKY_FORK=0).
+ * Both give bit-identical frames.  Negative: an error. */
+int rt_sky_forked(const Rust_WorldHandle *handle, int device);
 
 /* Diagnostics: which trace-kernel instances were launched on `device` (-1 =
  * current) since the set was last cleared -- by frames, accumulation and

@@ -219,6 +219,14 @@ int rt_sky_rows(const Rust_WorldHandle *h, int device) {
     return rtamd::sky_rows(h->world->state, device);
 }
 
+int rt_sky_forked(const Rust_WorldHandle *h, int device) {
+    if (!h || !h->world) {
+        rtamd::set_error("rt_sky_forked: null argument");
+        return -1;
+    }
+    return rtamd::sky_forked(h->world->state, device);
+}
+
 int rt_leaf_defer(const Rust_WorldHandle *h, int device) {
     if (!h || !h->world) {
         rtamd::set_error("rt_leaf_defer: null argument");

@@ -53,6 +53,13 @@ public:
 class DevStream : public DevHandle<hipStream_t, hipStreamDestroy> {
 public:
     hipError_t create() { return h_ ? hipSuccess : hipStreamCreateWithFlags(&h_, hipStreamNonBlocking); }
+    // ... at the lowest priority the device offers: work that fills what other streams leave idle
+    hipError_t create_lowest_priority() {
+        if (h_) return hipSuccess;
+        int least = 0, greatest = 0;
+        const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        return e != hipSuccess ? e : hipStreamCreateWithPriority(&h_, hipStreamNonBlocking, least);
+    }
 };
 
 // The end of the last work enqueued on something shared, and the stream it

@@ -131,6 +131,7 @@ struct FrameValues {
     bool primary_lists = false;        // the frame's primary rays use candidate lists (spheres or triangles)
     SkyRows dev_sky;                   // ... and, with the device's lists, the sky rows classified with them
     SkyRows sky;                       // the rows this frame gives the sky kernel (choose_sky_rows; none: all traced)
+    bool sky_fork = false;             // ... which may run beside the trace launches, on the device's side stream
     bool use_tbvh = false;             // bind_triangle_search
     int ptl_where = 0;                 // rt_primary_tri_lists: 0 none, 1 host build, 2 device build
     float inv_spp = 0.0f;
@@ -463,15 +464,51 @@ int choose_kernel_instance(DeviceState *d, const SerialPass *sp, const AccumPass
 // would be the background and nothing else -- COUNTER, one rank, a sphere-only
 // scene searched by the tree with primary lists, fused resolve, no counters,
 // no pass, depth >= 1 (a frame of depth <= 0 is black).  RT_AMD_SKY_ROWS=0:
-// every row is traced (A/B runs and tests).
+// every row is traced (A/B runs and tests).  RT_AMD_SKY_FORK=0: the sky kernel
+// stays on the frame's stream, in front of the trace launches.
 void choose_sky_rows(const DeviceState *d, const SerialPass *sp, const AccumPass *ap, FrameValues &f,
                      const TraceParams &p) {
     f.sky = SkyRows{};
+    f.sky_fork = false;
     if (sp || ap || f.timed || !f.fused || f.replay || f.nranks != 1 || d->ntri != 0 || !f.use_bvh ||
         !f.primary_lists || p.depth < 1 || p.ablate != 0 || env_u64("RT_AMD_SKY_ROWS", 1) == 0)
         return;
     f.sky = f.dev_sky;
+    f.sky_fork = env_u64("RT_AMD_SKY_FORK", 1) != 0;
 }
+
+// s is capturing into a graph (a query that fails counts as capturing: what a
+// captured frame does is right for every frame)
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
+// The join of a frame that forked: the frame's stream waits for the end of what
+// the side stream holds.  Armed once that stream may hold work; a path that
+// leaves enqueue_launches early (a failed launch) then still joins, and records
+// the device's fence behind the join, so no work stays on the side stream that
+// the caller's stream and `done` do not follow.
+class SkyJoin {
+public:
+    SkyJoin(DeviceState *d, hipStream_t s) : d_(d), s_(s) {}
+    SkyJoin(const SkyJoin &) = delete;
+    SkyJoin &operator=(const SkyJoin &) = delete;
+    ~SkyJoin() {
+        if (armed_ && join() == hipSuccess) (void)d_->done.record(s_);
+    }
+    void arm() { armed_ = true; }
+    hipError_t join() {
+        armed_ = false;
+        const hipError_t e = d_->sky_join.record(d_->sky_stream.get());
+        return e != hipSuccess ? e : d_->sky_join.wait(s_);
+    }
+
+private:
+    DeviceState *d_;
+    hipStream_t s_;
+    bool armed_ = false;
+};
 
 // launch_trace, with the instance it ran noted in the device's set (rt_trace_launched)
 hipError_t launch_recorded(DeviceState *d, TraceVariant v, const TraceParams &p, const TraceTail &tail,
@@ -646,13 +683,25 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
     const size_t units_per_slab =
         adapt ? (size_t)std::min<uint64_t>(std::max<uint64_t>(1, f.slab_jobs / spp), std::max<size_t>(units, 1))
               : f.rows_per_slab;
-    // the sky rows first, in their own kernel on the same stream: the trace
-    // launches take the rows between the two blocks (none: no trace launch, and
-    // rt_trace_plain, rt_leaf_defer and rt_trace_launched keep saying what the
-    // last trace launch ran)
+    // the sky rows in their own kernel: the trace launches take the rows between
+    // the two blocks (none: no trace launch, and rt_trace_plain, rt_leaf_defer and
+    // rt_trace_launched keep saying what the last trace launch ran)
     const size_t row_lo = f.sky.top, row_hi = units - f.sky.bottom;
     d->last_sky_rows = f.sky.top + f.sky.bottom;
-    if (d->last_sky_rows) HIP_TRY(launch_sky_rows(p, f.sky.top, f.sky.bottom, s));
+    // With trace launches to run beside, the sky kernel goes to the device's side
+    // stream, behind this point of s (what s holds may still use d_out): it is
+    // enqueued after the trace launches and at the lowest priority, so their
+    // workgroups are placed first, and its waves take the slots that the trace
+    // launch's last waves leave idle.  A capturing stream keeps
+    // the one-stream order, so a captured frame has no parallel branches.
+    const bool fork = d->last_sky_rows && row_lo < row_hi && f.sky_fork && !stream_capturing(s);
+    d->last_sky_forked = fork;
+    SkyJoin sky(d, s);
+    if (fork) {
+        HIP_TRY(d->sky_fork.record(s));
+    } else if (d->last_sky_rows) {
+        HIP_TRY(launch_sky_rows(p, f.sky.top, f.sky.bottom, s));
+    }
     uint32_t &nslab = done.nslab;  // (counted frames: event triple per launch)
     for (size_t r0 = row_lo; r0 < row_hi; r0 += units_per_slab, ++nslab) {
         const size_t rows = std::min(units_per_slab, row_hi - r0);
@@ -718,6 +767,12 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             HIP_TRY(launch_resolve_ex(d->samples.get(), d_out, (uint32_t)(rows * width), spp, f.inv_spp,
                                       (uint32_t)width, (uint32_t)r0, s));
         if (timed) HIP_TRY(hipEventRecord(ev3[2].get(), s));
+    }
+    if (fork) {
+        HIP_TRY(d->sky_fork.wait(d->sky_stream.get()));
+        sky.arm();
+        HIP_TRY(launch_sky_rows(p, f.sky.top, f.sky.bottom, d->sky_stream.get()));
+        HIP_TRY(sky.join());
     }
     HIP_TRY(d->done.record(s));
     if (ap) HIP_TRY(ap->acc->done.record(s));
@@ -936,6 +991,14 @@ int sky_rows(WorldState &w, int device) {
     int rc = device_for(w, device, d);
     if (rc) return rc;
     return (int)d->last_sky_rows;
+}
+
+int sky_forked(WorldState &w, int device) {
+    std::lock_guard<std::recursive_mutex> lock(w.mu);  // (device_for may add a device)
+    DeviceState *d = nullptr;
+    int rc = device_for(w, device, d);
+    if (rc) return rc;
+    return d->last_sky_forked ? 1 : 0;
 }
 
 int trace_launched(WorldState &w, int device, uint8_t *out, size_t n, bool clear) {

@@ -132,6 +132,12 @@ struct DeviceState {
     DevBuf<uint32_t> gath;                                      // multi-device root: gathered tiles
     DevBuf<uint32_t> first_hit;                                 // first-hit records / views (host path)
     Fence done;                      // the last work enqueued on the scratch and the scene arrays
+    // A frame's sky kernel beside its trace launches (frame.cpp enqueue_launches):
+    // the side stream (lowest priority; created with the library's stream at device
+    // set-up), the point of the frame's stream it starts behind and its end, which
+    // the frame's stream waits for before it records `done`
+    DevStream sky_stream;
+    Fence sky_fork, sky_join;
     DevBuf<uint32_t> replay;
     // SERIAL mode (render_frame_serial): start states, candidate offsets, the
     // stream window of a chunk, xorshift jump matrices, control block
@@ -195,6 +201,7 @@ struct DeviceState {
     int last_leaf_defer = 0;                                    // its walk's pending leaves per lane (rt_leaf_defer)
     bool last_plain = false;                                    // it ran the plain instance (rt_trace_plain)
     uint32_t last_sky_rows = 0;                                 // rows the last frame launch gave the sky kernel (rt_sky_rows)
+    bool last_sky_forked = false;                               // ... and that kernel ran on sky_stream (rt_sky_forked)
     // the instances launched on this device since the last clear, one byte per
     // render.h trace_key (rt_trace_launched): frames, passes and SERIAL passes
     uint8_t trace_launched[kTraceKeys] = {};
@@ -494,6 +501,7 @@ long read_samples(WorldState &w, int device, float *out, size_t n);
 int leaf_defer(WorldState &w, int device);
 int trace_plain(WorldState &w, int device);
 int sky_rows(WorldState &w, int device);
+int sky_forked(WorldState &w, int device);
 // the device's set of launched instances into out (n bytes at most, one per
 // render.h trace_key; out may be null), cleared afterwards when asked -> kTraceKeys
 // (rt_trace_launched)

@@ -40,6 +40,7 @@ EXPORTS = (
     "rt_adapt_default_options", "rt_adapt_enable", "rt_adapt_disable", "rt_adapt_active",
     "rt_adapt_read_counts", "rt_adapt_read_sumsq", "rt_adapt_read_active", "rt_leaf_defer",
     "rt_trace_plain", "rt_trace_launched", "rt_trace_instances", "rt_sky_rows",
+    "rt_sky_forked",
     "rt_camera_new_with_vertical_fov", "rt_camera_new_look_at", "rt_camera_from_floats",
     "rt_camera_translate", "rt_camera_free", "rt_primary_tri_lists", "rt_camera_record_builds",
     "rt_first_hit_default_options", "rt_first_hit", "rt_first_hit_device", "rt_first_hit_pick",
@@ -222,6 +223,9 @@ def lib(path=None):
         if hasattr(L, "rt_sky_rows"):  # (likewise)
             L.rt_sky_rows.restype = C.c_int
             L.rt_sky_rows.argtypes = [H, C.c_int]
+        if hasattr(L, "rt_sky_forked"):  # (likewise)
+            L.rt_sky_forked.restype = C.c_int
+            L.rt_sky_forked.argtypes = [H, C.c_int]
         if hasattr(L, "rt_trace_launched"):  # (likewise)
             L.rt_trace_launched.restype = C.c_int
             L.rt_trace_launched.argtypes = [H, C.c_int, C.POINTER(C.c_uint8), C.c_size_t, C.c_int]
@@ -587,6 +591,14 @@ class World:
         n = self._L.rt_sky_rows(self._h, device)
         if n < 0:
             raise RenderError(f"rt_sky_rows failed ({n}): {self._L.rt_last_error().decode()}")
+        return n
+
+    def sky_forked(self, device=-1):
+        """rt_sky_forked: 1 when the last frame launch ran its sky kernel on the
+        library's side stream, beside the trace launches, else 0."""
+        n = self._L.rt_sky_forked(self._h, device)
+        if n < 0:
+            raise RenderError(f"rt_sky_forked failed ({n}): {self._L.rt_last_error().decode()}")
         return n
 
     def trace_launched(self, clear=False, device=-1):
