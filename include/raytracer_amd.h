@@ -177,8 +177,44 @@ int rt_render_ex(Rust_CFramebuffer framebuffer, const Rust_WorldHandle *handle,
  * consecutive frames and the caller's collectives pipeline -- except in
  * RT_RNG_SERIAL mode, whose start-state search reads its progress back and
  * waits on the host between batches of iterations (the REPLAY render that
- * follows is only enqueued); do not call it inside a stream capture.  Returns
- * 0 or a negative error. */
+ * follows is only enqueued).  Returns 0 or a negative error.
+ *
+ * Capture.  A call whose `hip_stream` is capturing into a HIP graph
+ * (hipStreamBeginCapture) records the frame instead of running it:
+ *  - What may be captured: rt_render_device with stats == NULL, ndevices == 0,
+ *    RT_RNG_COUNTER or RT_RNG_REPLAY, on a stream of the caller's.  Nothing
+ *    else is promised.  With stats, in RT_RNG_SERIAL mode or with ndevices >= 1
+ *    the call returns a negative error on a capturing stream, and so does
+ *    rt_accum_add_device (a pass's first sample index would be baked into the
+ *    graph: every replay would add the same samples again).  The first-hit,
+ *    filter and history device entries are not promised inside a capture.
+ *  - Warm rule: the same request must have been rendered outside a capture on
+ *    that device since the world's last camera change, resize or scene edit.
+ *    The same request: frame size, camera, accel, flags, samples per pixel and
+ *    bounces (with the environment knobs unchanged), and in REPLAY mode the
+ *    table's size; the seed may differ.  Warm means that the primary lists are
+ *    current, every buffer is large enough and the kernels are loaded -- render
+ *    the frame twice before capturing it and the capture also has the sky rows
+ *    of the frames that follow the first.
+ *  - A capturing call that is not warm returns a negative error whose message
+ *    says "render this frame once outside the capture first".  It enqueues
+ *    nothing (the capture stays valid and gets no node from it), allocates
+ *    nothing and changes none of the library's bookkeeping.
+ *  - REPLAY: the graph holds a copy node that reads the caller's replay_states
+ *    table at every launch.  Keep the table alive and unchanged for the graph's
+ *    lifetime.
+ *  - Lifetime: the graph's nodes name the world's device buffers and the
+ *    per-camera lists of the frame it recorded.  The library keeps those for
+ *    the graph across later camera changes, resizes and other requests (it
+ *    moves them aside instead of rewriting or freeing them, so every captured
+ *    camera and size holds its lists' memory until the next edit or free):
+ *    graphs of several cameras or sizes of one world can be launched in turn.
+ *    A scene edit (rt_world_set_*_material) and rt_free_world release
+ *    everything: destroy the graph before the edit or the free, and do not
+ *    launch it afterwards.
+ *  - Ordering: the ordering between streams described above covers calls, not
+ *    replays.  Order every graph launch against the other work on that world's
+ *    device yourself, by launching on the same stream or with events. */
 int rt_render_device(const Rust_WorldHandle *handle, size_t width, size_t height,
                      const RtRenderOptions *opts, void *d_rgba, void *hip_stream,
                      RtRenderStats *stats);
@@ -246,8 +282,9 @@ int rt_accum_add(RtAccum *acc, int64_t nsamples, Rust_ColorU8 *pixels, RtRenderS
  * hip_stream (NULL = the library's stream).  With stats == NULL the pass is
  * only enqueued (no host wait), like rt_render_device -- except on an adaptive
  * accumulator (rt_adapt_enable below), whose deciding passes read the new list
- * length back and wait on the host, as RT_RNG_SERIAL does in rt_render_device;
- * do not call those inside a stream capture. */
+ * length back and wait on the host, as RT_RNG_SERIAL does in rt_render_device.
+ * On a capturing stream every pass is refused with a negative error
+ * (rt_render_device, "Capture"). */
 int rt_accum_add_device(RtAccum *acc, int64_t nsamples, void *d_rgba, void *hip_stream,
                         RtRenderStats *stats);
 /* Samples per pixel held (0 after a reset, also one that the next add would
@@ -295,8 +332,7 @@ void rt_accum_free(RtAccum *acc);
  *
  * A deciding pass reads the new list length back (4 bytes) and therefore
  * waits on the host for the pass, also with stats == NULL in
- * rt_accum_add_device -- like RT_RNG_SERIAL in rt_render_device; do not call
- * it inside a stream capture. */
+ * rt_accum_add_device -- like RT_RNG_SERIAL in rt_render_device. */
 typedef struct RtAdaptOptions {
   float tolerance;       /* relative standard error of the mean to stop at      */
   float bias;            /* added to the mean: dark pixels stop on an absolute  */

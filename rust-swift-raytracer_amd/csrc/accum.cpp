@@ -135,6 +135,8 @@ void accum_free(AccumState *a) {
 int accum_add(AccumState &a, const CameraModel &cam, int64_t nsamples, uint32_t *d_out, hipStream_t stream,
               void *host_out, RtRenderStats *stats) {
     if (stats) std::memset(stats, 0, sizeof(*stats));
+    // (a captured pass would bake its n0 in: every replay would add the same samples again)
+    if (stream_capturing(stream)) return refuse_capture("rt_accum_add_device", "an accumulation pass");
     WorldState *wp = accum_world(a);
     if (!wp) return -1;
     WorldState &w = *wp;

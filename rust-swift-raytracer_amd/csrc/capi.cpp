@@ -194,6 +194,8 @@ int rt_render_device(const Rust_WorldHandle *h, size_t width, size_t height,
         return -1;
     }
     RtRenderOptions o = opts ? *opts : reference_options();
+    if (o.ndevices >= 1 && rtamd::stream_capturing(static_cast<hipStream_t>(hip_stream)))
+        return rtamd::refuse_capture("rt_render_device", "a frame tiled over devices (ndevices >= 1)");
     if (o.ndevices >= 1)
         return rtamd::render_frame_multi(h->world->state, h->camera->cam, width, height, o,
                                          static_cast<uint32_t *>(d_rgba),

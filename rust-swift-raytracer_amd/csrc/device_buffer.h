@@ -22,12 +22,14 @@ public:
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : ptr_(o.ptr_), cap_(o.cap_) { o.ptr_ = nullptr; o.cap_ = 0; }
+    DevBuf(DevBuf &&o) noexcept : ptr_(o.ptr_), cap_(o.cap_), pinned_(o.pinned_) {
+        o.ptr_ = nullptr; o.cap_ = 0; o.pinned_ = false;
+    }
     DevBuf &operator=(DevBuf &&o) noexcept {
         if (this != &o) {
             reset();
-            ptr_ = o.ptr_; cap_ = o.cap_;
-            o.ptr_ = nullptr; o.cap_ = 0;
+            ptr_ = o.ptr_; cap_ = o.cap_; pinned_ = o.pinned_;
+            o.ptr_ = nullptr; o.cap_ = 0; o.pinned_ = false;
         }
         return *this;
     }
@@ -41,7 +43,14 @@ public:
         if (ptr_) (void)(Pinned ? hipHostFree(ptr_) : hipFree(ptr_));
         ptr_ = nullptr;
         cap_ = 0;
+        pinned_ = false;
     }
+
+    // Held: a graph's nodes name this memory (a captured frame bound it), so its
+    // owner moves the buffer aside instead of rewriting, growing or freeing it
+    // (runtime.h DeviceState::retire).  The mark goes with the memory.
+    void hold() { pinned_ = ptr_ != nullptr; }
+    bool held() const { return pinned_; }
 
     // Room for n elements: a no-op when n <= cap(), else the old memory is
     // freed and new memory allocated (contents discarded); empty on failure.
@@ -71,6 +80,7 @@ public:
 private:
     T *ptr_ = nullptr;
     size_t cap_ = 0;
+    bool pinned_ = false;
 };
 
 template <typename T>

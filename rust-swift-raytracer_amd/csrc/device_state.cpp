@@ -260,10 +260,14 @@ int select_device(int want, int &dev, const char *who) {
     return 0;
 }
 
-int device_for(WorldState &w, int want, DeviceState *&out) {
+int device_for(WorldState &w, int want, DeviceState *&out, bool capturing) {
     int dev = -1;
     int rc = select_device(want, dev);
     if (rc) return rc;
+    if (capturing) {
+        const auto it = w.devices.find(dev);
+        if (it == w.devices.end() || !it->second) return cold_request("the world is not on this device yet");
+    }
     auto &slot = w.devices[dev];
     if (!slot) {
         auto d = std::make_unique<DeviceState>();
@@ -285,7 +289,7 @@ int device_for(WorldState &w, int want, DeviceState *&out) {
         if (rc) return rc;
         rc = upload_triangle_trees(w, d.get());
         if (rc) return rc;
-        HIP_TRY(d->counter.grow(2 * kMaxParts * 32));
+        HIP_TRY(d->counter.grow(3 * kMaxParts * 32));
         slot = std::move(d);
     }
     out = slot.get();

@@ -75,7 +75,7 @@ int first_hit(WorldState &w, const CameraModel &cam, size_t width, size_t height
     TraceParams p{};
     bind_scene_arrays(d, cam, width, height, p);
     if (d->nnodes > 0 && r.o.accel != RT_ACCEL_BRUTE) bind_sphere_tree(w, d, p);
-    rc = bind_primary_triangle_search(w, d, cam, width, height, r.o.accel, stream, s, p);
+    rc = bind_primary_triangle_search(w, d, cam, width, height, r.o.accel, s, p);
     if (rc) return rc;
     // the lists' strip of a pixel comes from its job (serial_jobs.h job_pixel):
     // one sample per pixel, one rank, job = top row * width + col

@@ -98,16 +98,32 @@ hipError_t wait_for_readers(bool buffer_exists) {
 
 // src into buf after wait_for_readers (synchronously: src is pageable and
 // rebuilt by the next camera), at least min_elems elements; an empty buf for
-// an empty src with no minimum: a null pointer means "none"
+// an empty src with no minimum: a null pointer means "none".  A capturing frame
+// can do none of this: it is cold if it gets here.  A buffer that a graph's
+// nodes name is moved aside first (DeviceState::retire), and a fresh one filled.
 template <typename T, typename U>
-hipError_t replace_contents(DevBuf<T> &buf, const std::vector<U> &src, size_t min_elems = 0) {
-    const hipError_t e = wait_for_readers((bool)buf);
-    if (e != hipSuccess) return e;
+int replace_contents(DeviceState *d, DevBuf<T> &buf, const std::vector<U> &src, bool capturing,
+                     size_t min_elems = 0) {
+    if (capturing) return cold_request("a per-camera array is not on the device yet");
+    d->retire(buf);
+    HIP_TRY(wait_for_readers((bool)buf));
     if (src.empty() && min_elems == 0) {
         buf.reset();
-        return hipSuccess;
+        return 0;
     }
-    return buf.upload(src, min_elems);
+    HIP_TRY(buf.upload(src, min_elems));
+    return 0;
+}
+
+// Room for n elements of a scratch buffer; a capturing frame takes it as it is,
+// and memory that a graph's nodes name is moved aside, not freed
+template <typename T>
+int grow_scratch(DeviceState *d, DevBuf<T> &buf, size_t n, bool capturing, const char *what) {
+    if (n <= buf.cap()) return 0;
+    if (capturing) return cold_request(what);
+    d->retire(buf);
+    HIP_TRY(buf.grow(n));
+    return 0;
 }
 
 // what check_frame_request found (negative: an error)
@@ -119,12 +135,14 @@ struct LaunchPlan { uint64_t blocks, nwaves, chunk, parts, block_threads; };
 
 // The values of a frame that are derived once, by the steps below in order
 struct FrameValues {
+    bool capturing = false;            // render_frame: the caller's stream is capturing into a graph
     uint32_t nranks = 1, B = 1;        // check_frame_request: ranks, rows per row block ...
     size_t T = 0;                      // ... and this rank's tile rows
     uint32_t spp = 0;                  // plan_sample_storage
     uint64_t jobs_per_row = 0, slab_jobs = 0;
     size_t rows_per_slab = 0;
     bool fused = false, replay = false;
+    size_t replay_upload = 0;          // the caller's REPLAY table goes to d->replay: its states (0: none)
     bool use_bvh = false;              // bind_sphere_search
     const uint4 *corner_img = nullptr; // the LDS tree as corner records (sphere-only frames), else box records
     TraceRequest want;                 // ... and what every launch asks for (render.h; kind: choose_kernel_instance)
@@ -181,10 +199,9 @@ int check_frame_request(const RtRenderOptions &o, size_t width, size_t height, c
     return kFrameRender;
 }
 
-// Fused resolve or slab, rows per launch, and the REPLAY table's upload
+// Fused resolve or slab, rows per launch, and room for the REPLAY table
 int plan_sample_storage(DeviceState *d, const RtRenderOptions &o, size_t width, size_t height,
-                        const SerialPass *sp, const uint32_t *d_replay, const AccumPass *ap, hipStream_t s,
-                        FrameValues &f) {
+                        const SerialPass *sp, const uint32_t *d_replay, const AccumPass *ap, FrameValues &f) {
     const uint32_t spp = o.samples_per_pixel > 0 ? (uint32_t)o.samples_per_pixel : 0u;
     const uint64_t jobs_per_row = (uint64_t)width * spp;
     if (jobs_per_row > 0x7FFFFFFFull) { set_error("width*spp too large"); return -1; }
@@ -200,13 +217,17 @@ int plan_sample_storage(DeviceState *d, const RtRenderOptions &o, size_t width, 
     size_t rows_per_slab = jobs_per_row ? (size_t)std::max<uint64_t>(1, slab_jobs / jobs_per_row) : f.T;
     rows_per_slab = std::min(rows_per_slab, f.T);
     if (jobs_per_row && !fused)
-        HIP_TRY(d->samples.grow(3 * rows_per_slab * jobs_per_row));
+        if (int rc = grow_scratch(d, d->samples, 3 * rows_per_slab * jobs_per_row, f.capturing,
+                                  "the sample slab is too small"))
+            return rc;
 
+    // (the table's copy is enqueued with the launches: enqueue_launches)
     const bool replay = d_replay != nullptr || o.rng_mode == RT_RNG_REPLAY;
     if (!d_replay && !sp && o.rng_mode == RT_RNG_REPLAY && spp) {
-        const size_t n = width * height * (size_t)spp;
-        HIP_TRY(d->replay.grow(n));
-        HIP_TRY(hipMemcpyAsync(d->replay.get(), o.replay_states, n * 4, hipMemcpyHostToDevice, s));
+        f.replay_upload = width * height * (size_t)spp;
+        if (int rc = grow_scratch(d, d->replay, f.replay_upload, f.capturing,
+                                  "the REPLAY table's buffer is too small"))
+            return rc;
     }
     f.spp = spp;
     f.jobs_per_row = jobs_per_row;
@@ -268,18 +289,19 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
         // sphere-only scenes: primary rays test their pixel's candidates
         if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 && gpu_lists()) {
             bool ok = false;
-            const int rc = device_sphere_lists(w, d, cam, width, height, s, ok);
+            const int rc = device_sphere_lists(w, d, cam, width, height, s, f.capturing, ok);
             if (rc) return rc;
             p.spl = ok ? d->gspl.lists.get() : nullptr;
             f.primary_lists = ok;
             if (ok) f.dev_sky = d->gspl.sky;
-        } else if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0 &&
-                   prepare_primary_sphere_lists(w, cam, width, height)) {
-            if (d->spl_version != w.spl_version) {
-                HIP_TRY(replace_contents(d->spl, w.spl.rec));
+        } else if (d->ntri == 0 && env_u64("RT_AMD_SPHERE_LISTS", 1) != 0) {
+            bool current = false;
+            if (int rc = prepare_primary_sphere_lists(w, cam, width, height, f.capturing, current)) return rc;
+            if (current && d->spl_version != w.spl_version) {
+                if (int rc = replace_contents(d, d->spl, w.spl.rec, f.capturing)) return rc;
                 d->spl_version = w.spl_version;
             }
-            p.spl = d->spl.get();
+            if (current) p.spl = d->spl.get();
             f.primary_lists = p.spl != nullptr;
         }
     }
@@ -288,40 +310,35 @@ int bind_sphere_search(WorldState &w, DeviceState *d, const CameraModel &cam, si
 
 // The triangle trees, the camera-origin records (uploaded when the origin
 // changed) and the primary strip lists: the device's, or the host's uploaded
-// (f.ptl_where says which; a capturing stream cannot build on the device)
+// (f.ptl_where says which).  A capturing frame finds all of them current, or is cold.
 int bind_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                         const RtRenderOptions &o, hipStream_t stream, hipStream_t s, FrameValues &f,
-                         TraceParams &p) {
+                         const RtRenderOptions &o, hipStream_t s, FrameValues &f, TraceParams &p) {
     f.use_tbvh = d->tnodes > 0 && o.accel != RT_ACCEL_BRUTE;
     const bool use_tbvh = f.use_tbvh;
     const bool want_ptl = width >= 2 && height >= 2 && env_u64("RT_AMD_PRIMARY_LISTS", 1) != 0;
-    // the lists on the device (the records alone on the host).  The build reads
-    // its lengths back, which a capturing stream cannot do: a captured frame
-    // uses the device lists only when they are current, else the host build
+    // the lists on the device (the records alone on the host)
     bool gpu_ptl = use_tbvh && want_ptl && gpu_tri_lists();
-    bool capturing = false;
-    if (gpu_ptl && stream) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        capturing = hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    }
+    const bool capturing = f.capturing;
+    // (the host's per-camera builds: milliseconds of work that a capture would not repeat)
+    if (use_tbvh && capturing &&
+        !(camera_current(w, cam, !gpu_ptl && !want_ptl) &&
+          (gpu_ptl || !want_ptl || !w.ctree_version || camera_lists_current(w, cam, width, height))))
+        return cold_request("the camera's triangle records are not built for this camera and size");
     if (use_tbvh && gpu_ptl) {
         prepare_camera(w, cam, false);
-        if (capturing && !d->gptl.current(cam, width, height, w.ctree_version)) {
-            gpu_ptl = false;
-            prepare_camera_lists(w, cam, width, height, true);
-        }
     } else if (use_tbvh) {
         prepare_camera_lists(w, cam, width, height, want_ptl);
     }
     if (use_tbvh && w.ctree_version && d->cam_version != w.ctree_version) {
         const CameraTriangleBVH &ct = w.ctree;
+        if (int rc = replace_contents(d, d->cam_tris, ct.tris, capturing)) return rc;
         d->cam_nnodes = 0;
-        HIP_TRY(replace_contents(d->cam_tris, ct.tris));
         if (ct.nodes.empty()) {  // (records only)
+            d->retire(d->cam_nodes);
             HIP_TRY(wait_for_readers((bool)d->cam_nodes));
             d->cam_nodes.reset();
         } else {
-            HIP_TRY(replace_contents(d->cam_nodes, ct.qnodes));
+            if (int rc = replace_contents(d, d->cam_nodes, ct.qnodes, capturing)) return rc;
             d->cam_nnodes = (uint32_t)(ct.qnodes.size() / 8);
         }
         d->cam_version = w.ctree_version;
@@ -335,10 +352,12 @@ int bind_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, 
             }
             bool dev_lists = false;
             if (gpu_ptl) {
-                const int rc = device_tri_lists(w, d, cam, width, height, s, dev_lists);
+                const int rc = device_tri_lists(w, d, cam, width, height, s, capturing, dev_lists);
                 if (rc) return rc;
                 if (d->gptl.host) {  // (beyond the kernels' range)
                     gpu_ptl = false;
+                    if (capturing && !camera_lists_current(w, cam, width, height))
+                        return cold_request("the primary triangle lists are not built for this camera and size");
                     prepare_camera_lists(w, cam, width, height, true);
                 }
             }
@@ -350,14 +369,17 @@ int bind_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, 
                 p.ptl_spr = d->gptl.spr;
                 p.ptl_always = d->gptl.total;
                 p.ptl_end = d->gptl.total + d->gptl.nalways;
-            } else if (!gpu_ptl && want_ptl && w.ptl_version && w.ptl_w == width && w.ptl_h == height &&
-                       w.ptl_ctree == w.ctree_version && same_cam(w.ptl_cam, cam)) {
+            } else if (!gpu_ptl && want_ptl && camera_lists_current(w, cam, width, height)) {
                 if (d->ptl_version != w.ptl_version) {
                     const PrimaryTriLists &pl = w.ptl;
-                    HIP_TRY(replace_contents(d->ptl_off, pl.offsets));
+                    if (int rc = replace_contents(d, d->ptl_off, pl.offsets, capturing)) return rc;
                     // (the items' pointer goes to the kernel even when there are none)
-                    if (d->ptl_off) HIP_TRY(replace_contents(d->ptl_items, pl.items, 1));
-                    else d->ptl_items.reset();
+                    if (d->ptl_off) {
+                        if (int rc = replace_contents(d, d->ptl_items, pl.items, capturing, 1)) return rc;
+                    } else {
+                        d->retire(d->ptl_items);
+                        d->ptl_items.reset();
+                    }
                     d->ptl_version = w.ptl_version;
                 }
                 if (d->ptl_off) {
@@ -477,13 +499,6 @@ void choose_sky_rows(const DeviceState *d, const SerialPass *sp, const AccumPass
     f.sky_fork = env_u64("RT_AMD_SKY_FORK", 1) != 0;
 }
 
-// s is capturing into a graph (a query that fails counts as capturing: what a
-// captured frame does is right for every frame)
-bool stream_capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-}
-
 // The join of a frame that forked: the frame's stream waits for the end of what
 // the side stream holds.  Armed once that stream may hold work; a path that
 // leaves enqueue_launches early (a failed launch) then still joins, and records
@@ -529,7 +544,7 @@ int launch_serial_pass(DeviceState *d, size_t width, size_t height, const RtRend
     if (njobs == 0) return 0;
     if (njobs > 0x7FFFFFFFull) { set_error("serial pass too large"); return -1; }
     if (sp->mode != kRngSerialCoalesce && sp->mode != kRngSerialPixel)
-        HIP_TRY(d->samples.grow(3 * njobs));
+        if (int rc = grow_scratch(d, d->samples, 3 * njobs, false, "")) return rc;
     p.samples = sp->mode == kRngSerialPixel ? sp->ptab : d->samples.get();
     p.sL = sp->L;
     p.sK = sp->Kmax;
@@ -649,10 +664,20 @@ LaunchPlan plan_launch(DeviceState *d, const TraceParams &p, const FrameValues &
     return LaunchPlan{blocks, nwaves, chunk, parts, wpb * 64};
 }
 
+// The sample rings of a fused launch with plan lp: log2 of a slot's samples, and the floats
+uint32_t ring_shift_for(const LaunchPlan &lp) {
+    uint32_t shift = 0;
+    while ((1ull << shift) < lp.chunk) ++shift;
+    return shift;
+}
+size_t ring_floats(const LaunchPlan &lp) { return lp.nwaves * 3 * ((size_t)kTraceRing << ring_shift_for(lp)); }
+
 // The frame's launches: slabs of rows (an adaptive pass: of list entries),
-// each on one of the two job-counter sets, then the end-of-frame events
-int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_out, const AccumPass *ap,
-                     hipStream_t s, const FrameValues &f, TraceParams &p, LaunchesDone &done) {
+// each on one of the two job-counter sets, then the end-of-frame events.
+// A capturing frame ("Capture"): every launch on the third set
+// behind a fill, the host's parity untouched, no fork and no fence recorded.
+int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_out, const uint32_t *replay_table,
+                     const AccumPass *ap, hipStream_t s, const FrameValues &f, TraceParams &p, LaunchesDone &done) {
     const uint32_t spp = f.spp;
     const bool fused = f.fused, timed = f.timed, adapt = f.want.kind == kKindAdapt;
     TraceTail tail;
@@ -687,6 +712,15 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
     // the two blocks (none: no trace launch, and rt_trace_plain, rt_leaf_defer and
     // rt_trace_launched keep saying what the last trace launch ran)
     const size_t row_lo = f.sky.top, row_hi = units - f.sky.bottom;
+    // (a capturing frame's rings are checked before its first node, not launch by launch)
+    if (f.capturing && fused)
+        for (size_t r0 = row_lo; r0 < row_hi; r0 += units_per_slab) {
+            const uint64_t njobs = std::min(units_per_slab, row_hi - r0) * jobs_per_unit;
+            if (njobs && ring_floats(plan_launch(d, p, f, f.tv, njobs)) > d->ring.cap())
+                return cold_request("the sample rings are too small");
+        }
+    if (f.replay_upload)
+        HIP_TRY(hipMemcpyAsync(d->replay.get(), replay_table, f.replay_upload * 4, hipMemcpyHostToDevice, s));
     d->last_sky_rows = f.sky.top + f.sky.bottom;
     // With trace launches to run beside, the sky kernel goes to the device's side
     // stream, behind this point of s (what s holds may still use d_out): it is
@@ -694,7 +728,7 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
     // workgroups are placed first, and its waves take the slots that the trace
     // launch's last waves leave idle.  A capturing stream keeps
     // the one-stream order, so a captured frame has no parallel branches.
-    const bool fork = d->last_sky_rows && row_lo < row_hi && f.sky_fork && !stream_capturing(s);
+    const bool fork = d->last_sky_rows && row_lo < row_hi && f.sky_fork && !f.capturing;
     d->last_sky_forked = fork;
     SkyJoin sky(d, s);
     if (fork) {
@@ -728,8 +762,9 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             p.ring = nullptr;
             p.ring_shift = 0;
             if (fused) {
-                while ((1ull << p.ring_shift) < chunk) ++p.ring_shift;
-                HIP_TRY(d->ring.grow(nwaves * 3 * (kTraceRing << p.ring_shift)));
+                p.ring_shift = ring_shift_for(lp);
+                if (int rc = grow_scratch(d, d->ring, ring_floats(lp), f.capturing, "the sample rings are too small"))
+                    return rc;
                 p.ring = d->ring.get();
             }
             p.nparts = (uint32_t)parts;
@@ -737,10 +772,12 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             // before it, or filled here) and zeroes the other for the next one,
             // so back-to-back frames need no fill launch (a fill plus its gap
             // before the trace kernel was ~20 us of every C2 frame)
-            uint32_t *const cur = d->counter.get() + (size_t)d->cset * kMaxParts * 32;
-            if (!d->cset_clean[d->cset]) HIP_TRY(hipMemsetAsync(cur, 0, parts * 128, s));
+            // (a captured launch runs any number of times, unseen: set 2 behind a fill node)
+            const uint32_t set = f.capturing ? 2u : d->cset;
+            uint32_t *const cur = d->counter.get() + (size_t)set * kMaxParts * 32;
+            if (f.capturing || !d->cset_clean[set]) HIP_TRY(hipMemsetAsync(cur, 0, parts * 128, s));
             p.job_counter = cur;
-            p.job_counter_next = d->counter.get() + (size_t)(d->cset ^ 1u) * kMaxParts * 32;
+            p.job_counter_next = f.capturing ? nullptr : d->counter.get() + (size_t)(set ^ 1u) * kMaxParts * 32;
             // the launch's instance, resolved once (chunk, ring and gj32 are set per launch)
             const TraceVariant v = resolve_trace_variant(p, f.want);
             if (adapt) tail.list = ap->list + r0;
@@ -749,9 +786,11 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
             d->last_leaf_defer = trace_leaf_defer(v);
             d->last_plain = v.leaf == TraceLeaf::Plain;
             d->last_ptl = f.ptl_where;
-            d->cset_clean[d->cset] = false;
-            d->cset ^= 1u;
-            d->cset_clean[d->cset] = true;
+            if (!f.capturing) {
+                d->cset_clean[d->cset] = false;
+                d->cset ^= 1u;
+                d->cset_clean[d->cset] = true;
+            }
             p.job_counter = d->counter.get();
             p.job_counter_next = nullptr;
             done.lean_plan =
@@ -774,9 +813,27 @@ int enqueue_launches(DeviceState *d, size_t width, size_t height, uint32_t *d_ou
         HIP_TRY(launch_sky_rows(p, f.sky.top, f.sky.bottom, d->sky_stream.get()));
         HIP_TRY(sky.join());
     }
-    HIP_TRY(d->done.record(s));
+    // (an event recorded on a capturing stream belongs to the graph: a later wait on
+    // it would draw the waiting stream into the capture; replays are the caller's to order)
+    if (!f.capturing) HIP_TRY(d->done.record(s));
     if (ap) HIP_TRY(ap->acc->done.record(s));
     return 0;
+}
+
+// What a captured frame's nodes name of the device state beyond the scene's
+// own arrays -- the scratch and the per-camera arrays it bound -- is held from
+// here on: a later camera, size or request that would rewrite, grow or free one
+// of them gets a fresh buffer (DeviceState::retire), and the graph stays valid.
+void hold_bound_buffers(DeviceState *d, const FrameValues &f, const TraceParams &p) {
+    if (f.fused) d->ring.hold();
+    else d->samples.hold();
+    if (f.replay_upload) d->replay.hold();
+    if (p.spl == d->gspl.lists.get()) d->gspl.lists.hold();
+    if (p.spl == d->spl.get()) d->spl.hold();
+    if (p.cam_tris) d->cam_tris.hold();
+    if (p.cam_nodes) d->cam_nodes.hold();
+    if (p.ptl_off == d->gptl.off.get()) d->gptl.off.hold(), d->gptl.items.hold();
+    if (p.ptl_off == d->ptl_off.get()) d->ptl_off.hold(), d->ptl_items.hold();
 }
 
 // A counted frame's pending record on its device (collect_frame_stats reads it)
@@ -829,11 +886,11 @@ int queue_frame_stats(DeviceState *d, hipStream_t s, const FrameValues &f, const
 // static tree and, where they apply, the camera-origin records and primary
 // strip lists, made current for (cam, width, height) as for a frame.
 int bind_primary_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                                 int32_t accel, hipStream_t stream, hipStream_t s, TraceParams &p) {
+                                 int32_t accel, hipStream_t s, TraceParams &p) {
     RtRenderOptions o{};
     o.accel = accel;
     FrameValues f;
-    return bind_triangle_search(w, d, cam, width, height, o, stream, s, f, p);
+    return bind_triangle_search(w, d, cam, width, height, o, s, f, p);
 }
 
 int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t height,
@@ -842,26 +899,34 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
                  const AccumPass *ap) {
     if (stats) std::memset(stats, 0, sizeof(*stats));
     FrameValues f;
+    // A caller's stream that is capturing into a graph (raytracer_amd.h, rt_render_device):
+    // the one query of the frame.  Such a frame is warm -- nothing below allocates,
+    // uploads, builds lists or waits on the host for it -- or refused as cold.
+    f.capturing = stream_capturing(stream);
+    if (f.capturing && stats) return refuse_capture("rt_render_device", "a frame with stats");
     int rc = check_frame_request(o, width, height, sp, d_replay, ap, d_out, f);
+    if (f.capturing && rc == kFrameSerial) return refuse_capture("rt_render_device", "a SERIAL frame");
     if (rc == kFrameSerial) return render_frame_serial(w, cam, width, height, o, d_out, stream, stats);
     if (rc) return rc < 0 ? rc : 0;
 
     std::lock_guard<std::recursive_mutex> lock(w.mu);
     DeviceState *d = nullptr;
-    rc = device_for(w, o.device, d);
+    rc = device_for(w, o.device, d, f.capturing);
     if (rc) return rc;
     hipStream_t s = stream ? stream : d->stream.get();
     // the device's scratch (job counters, rings, slab, stats) is shared by every
     // frame on it: a frame enqueued on another stream waits for the last one
-    HIP_TRY(d->done.wait(s));
+    // (a capturing frame enqueues nothing that runs now, and its replays are the
+    // caller's to order: no wait node, and no wait on an event outside the capture)
+    if (!f.capturing) HIP_TRY(d->done.wait(s));
 
-    rc = plan_sample_storage(d, o, width, height, sp, d_replay, ap, s, f);
+    rc = plan_sample_storage(d, o, width, height, sp, d_replay, ap, f);
     if (rc) return rc;
     TraceParams p{};
     bind_scene(d, cam, width, height, o, sp, d_replay, f, p);
     rc = bind_sphere_search(w, d, cam, width, height, o, sp, s, f, p);
     if (rc) return rc;
-    rc = bind_triangle_search(w, d, cam, width, height, o, stream, s, f, p);
+    rc = bind_triangle_search(w, d, cam, width, height, o, s, f, p);
     if (rc) return rc;
     // (an accumulation pass writes the frame of all N = n0 + n samples held after it)
     const uint32_t nheld = ap ? ap->n0 + f.spp : f.spp;
@@ -877,8 +942,9 @@ int render_frame(WorldState &w, const CameraModel &cam, size_t width, size_t hei
     choose_sky_rows(d, sp, ap, f, p);
 
     LaunchesDone done;
-    rc = enqueue_launches(d, width, height, d_out, ap, s, f, p, done);
+    rc = enqueue_launches(d, width, height, d_out, o.replay_states, ap, s, f, p, done);
     if (rc) return rc;
+    if (f.capturing) hold_bound_buffers(d, f, p);
     classify_pending_sky_rows(w, d);  // (for the next frame, while the device runs this one)
     // without stats the frame stays asynchronous on the stream (no host wait)
     if (!f.timed) return 0;

@@ -12,14 +12,20 @@ static uint32_t cam_leaf() {
     return (uint32_t)env_u64("RT_AMD_CAM_LEAF", 2);  // triangles per camera-tree leaf
 }
 
+// prepare_camera below has nothing to build (a capturing frame asks before it calls)
+bool camera_current(const WorldState &w, const CameraModel &cam, bool tree) {
+    if (w.tbvh.nodes.empty() || env_u64("RT_AMD_CAMERA_TREE", 1) == 0) return true;
+    const float o[3] = {cam.origin.x, cam.origin.y, cam.origin.z};
+    return w.ctree_version && std::memcmp(o, w.ctree.origin, sizeof(o)) == 0 && (w.ctree_full || !tree);
+}
+
 // The camera-origin phantom records (and, with tree, the camera tree over
 // them) for cam's origin.  Frames with primary strip lists need only the
 // records: the lists replace every bounce-0 walk (C5: ~3 ms instead of the
 // tree's ~50 ms after a camera move).
 void prepare_camera(WorldState &w, const CameraModel &cam, bool tree) {
-    if (w.tbvh.nodes.empty() || env_u64("RT_AMD_CAMERA_TREE", 1) == 0) return;
+    if (camera_current(w, cam, tree)) return;
     const float o[3] = {cam.origin.x, cam.origin.y, cam.origin.z};
-    if (w.ctree_version && std::memcmp(o, w.ctree.origin, sizeof(o)) == 0 && (w.ctree_full || !tree)) return;
     w.ctree = build_camera_triangle_bvh(w.scene.triangles, w.packed.tri_hot, w.tbvh, o, cam_leaf(), tree);
     w.ctree_full = tree;
     ++w.ctree_version;
@@ -38,6 +44,12 @@ static bool job_ready(const std::future<T> &f) {
     return f.valid() && f.wait_for(std::chrono::seconds(0)) == std::future_status::ready;
 }
 
+// the host's primary strip lists are those of (cam, width, height) and the camera records
+bool camera_lists_current(const WorldState &w, const CameraModel &cam, size_t width, size_t height) {
+    return w.ptl_version && w.ptl_w == width && w.ptl_h == height && w.ptl_ctree == w.ctree_version &&
+           same_cam(w.ptl_cam, cam);
+}
+
 // Camera tree (bounce-0 triangle tree for the camera origin) and the primary
 // strip lists for (cam, width, height), rebuilt before the frame when either
 // changed.  Unlike the sphere lists these are not deferred to a host thread:
@@ -46,9 +58,7 @@ static bool job_ready(const std::future<T> &f) {
 void prepare_camera_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height, bool lists) {
     prepare_camera(w, cam, !lists);
     if (!lists || !w.ctree_version) return;
-    if (w.ptl_version && w.ptl_w == width && w.ptl_h == height && w.ptl_ctree == w.ctree_version &&
-        same_cam(w.ptl_cam, cam))
-        return;
+    if (camera_lists_current(w, cam, width, height)) return;
     w.ptl = build_primary_tri_lists(w.ctree, cam, width, height);
     w.ptl_cam = cam;
     w.ptl_w = width;
@@ -58,15 +68,17 @@ void prepare_camera_lists(WorldState &w, const CameraModel &cam, size_t width, s
 }
 
 // Primary sphere candidates per pixel (< 50 ms at 1080p on one host core).
-// Returns true when w.spl is current for (cam, width, height).
-bool prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height) {
-    if (w.spl_version && w.spl_w == width && w.spl_h == height && same_cam(w.spl_cam, cam))
-        return true;
+// current: w.spl is current for (cam, width, height) on return.
+int prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height, bool capturing,
+                                 bool &current) {
+    current = w.spl_version && w.spl_w == width && w.spl_h == height && same_cam(w.spl_cam, cam);
+    if (current) return 0;
+    if (capturing) return cold_request("the primary sphere lists are not built for this camera and size");
     WorldState::SplJob &j = w.spl_job;
     if (sync_lists()) {
         w.spl = build_primary_sphere_lists(w.bvh, cam, width, height);
     } else {
-        if (j.f.valid() && !job_ready(j.f)) return false;  // (one build at a time)
+        if (j.f.valid() && !job_ready(j.f)) return 0;  // (one build at a time)
         if (j.f.valid() && same_cam(j.cam, cam) && j.w == width && j.h == height) {
             w.spl = j.f.get();
         } else {
@@ -77,26 +89,29 @@ bool prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t 
             j.f = std::async(std::launch::async, [&w, cam, width, height]() {
                 return build_primary_sphere_lists(w.bvh, cam, width, height);
             });
-            return false;
+            return 0;
         }
     }
     w.spl_cam = cam;
     w.spl_w = width;
     w.spl_h = height;
     ++w.spl_version;
-    return true;
+    current = true;
+    return 0;
 }
 // The device build of the primary sphere lists for (cam, width, height),
 // enqueued on s when either changed; false = no lists (every primary ray
 // walks).  RT_AMD_SPL_CHECK=1 (tests): compare them with the host build.
 int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                        hipStream_t s, bool &ok) {
+                        hipStream_t s, bool capturing, bool &ok) {
     auto &g = d->gspl;
     if (!g.current(cam, width, height)) {
+        if (capturing) return cold_request("the primary sphere lists are not built for this camera and size");
         SphereListParams sp;
         g.ok = sphere_list_params(w.bvh, cam, width, height, sp) && (height + 15) / 16 <= 65535 &&
                      sp.n == d->nprims;
         if (g.ok) {
+            d->retire(g.lists);  // (a graph's nodes may name the old camera's lists)
             HIP_TRY(g.lists.grow(width * height));
             HIP_TRY(g.rects.grow((size_t)sp.n));
             HIP_TRY(g.flag.grow(1));
@@ -155,9 +170,10 @@ bool gpu_tri_lists() { return env_u64("RT_AMD_GPU_TRI_LISTS", 1) != 0; }
 // (g.host: the sizes are beyond the kernels' range and the host builds).
 // RT_AMD_PTL_CHECK=1 (tests): compare the three arrays with the host build.
 int device_tri_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                     hipStream_t s, bool &ok) {
+                     hipStream_t s, bool capturing, bool &ok) {
     auto &g = d->gptl;
     if (!g.current(cam, width, height, w.ctree_version)) {
+        if (capturing) return cold_request("the primary triangle lists are not built for this camera and size");
         const CameraTriangleBVH &ct = w.ctree;
         TriListParams tp;
         g.built = false;
@@ -178,6 +194,7 @@ int device_tri_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size
             HIP_TRY(g.rects.grow((size_t)tp.n));
             HIP_TRY(g.alw.grow((size_t)tp.n));
             HIP_TRY(g.count.grow(ncells));
+            d->retire(g.off), d->retire(g.items);  // (a graph's nodes may name the old lists)
             HIP_TRY(g.off.grow(ncells + 1));
             HIP_TRY(g.meta.grow(4));
             HIP_TRY(g.hmeta.grow(4));

@@ -157,9 +157,11 @@ struct DeviceState {
     DevBuf<uint32_t> sjump;
     DevBuf<uint32_t> sctrl;
     DevBuf<unsigned long long> scheck;                          // chain-check count
-    DevBuf<uint32_t> counter;                                   // job counters: 2 sets of kMaxParts
-    uint32_t cset = 0;              // the set the next frame launch uses ...
+    DevBuf<uint32_t> counter;                                   // job counters: 3 sets of kMaxParts
+    uint32_t cset = 0;              // the set (0 or 1) the next frame launch uses ...
     bool cset_clean[2] = {false, false};  // ... and whether each set is known to be zero
+    // (set 2: the launches captured into a graph, which run when the host does not
+    // see them; each fills it first and leaves cset and cset_clean alone)
     DevBuf<unsigned long long> stats;                           // per-wave counter records
     // resident workgroups per CU of the scene's kernel instances, by render.h
     // trace_key less the mesh: a device holds one scene, whose frames all plan
@@ -205,6 +207,15 @@ struct DeviceState {
     // the instances launched on this device since the last clear, one byte per
     // render.h trace_key (rt_trace_launched): frames, passes and SERIAL passes
     uint8_t trace_launched[kTraceKeys] = {};
+    // Buffers that captured frames bound (DevBuf::hold) and that a later camera,
+    // size or request would have rewritten, grown or freed: moved here instead,
+    // with their memory, and freed with the device state.  A graph's nodes so
+    // stay valid until the scene is edited or the world freed ("Capture").
+    std::vector<std::shared_ptr<void>> retired;
+    template <typename T>
+    void retire(DevBuf<T> &buf) {
+        if (buf.held()) retired.push_back(std::make_shared<DevBuf<T>>(std::move(buf)));
+    }
     ~DeviceState();
 };
 

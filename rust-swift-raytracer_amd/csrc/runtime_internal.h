@@ -67,12 +67,30 @@ static_assert(kPrimaryTriStripW == kTriStripW, "render.h and bvh.h strip widths"
 static constexpr uint64_t kMaxParts = kMaxJobParts;  // job-queue partitions (render.h)
 static constexpr uint32_t kPixtabParts = 64;  // the pixel table pass's (zeroed by the window kernel)
 
+// ---- stream capture (raytracer_amd.h, rt_render_device: "Capture")
+// s is capturing into a graph (null: no; a query that fails counts as capturing)
+inline bool stream_capturing(hipStream_t s) {
+    if (!s) return false;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+// a call that is never captured (stats, SERIAL, several devices, accumulation) -> -1
+inline int refuse_capture(const char *who, const char *what) {
+    return fail(who, std::string(what) + " cannot be captured into a graph");
+}
+// a capturing frame that is not warm: it would have to allocate, upload, build
+// lists or wait on the host here (what) -> -1, with nothing enqueued or changed
+inline int cold_request(const char *what) {
+    return fail("capture", std::string(what) + ": render this frame once outside the capture first");
+}
+
 // device_state.cpp: device `want` (< 0: the current one) counted, range-checked
 // and selected -> dev (who: a prefix for the messages, none for null)
 int select_device(int want, int &dev, const char *who = nullptr);
 // ... and w's state on it, created on first use -- stream and events, the
-// scene upload, the LDS layout and occupancy decisions
-int device_for(WorldState &w, int want, DeviceState *&out);
+// scene upload, the LDS layout and occupancy decisions (capturing: a cold
+// request where there is none yet)
+int device_for(WorldState &w, int want, DeviceState *&out, bool capturing = false);
 
 // frame.cpp: the parts of a TraceParams that do not depend on the kind of
 // launch -- the scene's arrays with the camera and the frame size, the sphere
@@ -82,21 +100,25 @@ void bind_sphere_tree(const WorldState &w, const DeviceState *d, TraceParams &p)
 void bind_triangle_tree(const WorldState &w, const DeviceState *d, TraceParams &p);
 // ... and a frame's whole triangle search for (cam, width, height): that tree
 // plus the camera-origin records and primary strip lists, rebuilt when the
-// camera, the frame size or the records changed (stream: the caller's, may be
-// null; s: the stream the launch goes to)
+// camera, the frame size or the records changed (s: the stream the launch goes to)
 int bind_primary_triangle_search(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                                 int32_t accel, hipStream_t stream, hipStream_t s, TraceParams &p);
+                                 int32_t accel, hipStream_t s, TraceParams &p);
 
 // primary_lists.cpp
 bool gpu_lists();      // RT_AMD_GPU_LISTS
 bool gpu_tri_lists();  // RT_AMD_GPU_TRI_LISTS
+// (what prepare_camera and prepare_camera_lists would find, without building anything)
+bool camera_current(const WorldState &w, const CameraModel &cam, bool tree);
+bool camera_lists_current(const WorldState &w, const CameraModel &cam, size_t width, size_t height);
 void prepare_camera_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height, bool lists);
-bool prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height);
+// (capturing, in these three: a cold request where something would be built)
+int prepare_primary_sphere_lists(WorldState &w, const CameraModel &cam, size_t width, size_t height, bool capturing,
+                                 bool &current);
 int device_sphere_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                        hipStream_t s, bool &ok);
+                        hipStream_t s, bool capturing, bool &ok);
 void classify_pending_sky_rows(WorldState &w, DeviceState *d);
 int device_tri_lists(WorldState &w, DeviceState *d, const CameraModel &cam, size_t width, size_t height,
-                     hipStream_t s, bool &ok);
+                     hipStream_t s, bool capturing, bool &ok);
 
 // serial_states.cpp
 int serial_check_args(size_t width, size_t height, const RtRenderOptions &o);

@@ -64,8 +64,8 @@ the filter's; a wait is fence.wait(stream), the host's wait fence.sync()):
       streams behind a pass        pass, then the first resolve's snapshots; f.done: the first
                                    resolve's staging; d->done), history_read_length (the host waits)
 Every wait on a fence in frame.cpp, accum.cpp, filter.cpp, first_hit.cpp, history.cpp and
-serial_states.cpp is reached by a case.  Stream capture has no test (graph replay
-is left to a change of its own).
+serial_states.cpp is reached by a case.  Frames captured into a graph and replayed, which
+the fences do not order, are in tests/test_gpu_capture.py.
 """
 import ctypes as C
 import os
