@@ -748,6 +748,22 @@ int rt_clamp_run(size_t width, size_t height, const RtHistoryOptions *opts,
                  const RtClampOptions *clamp, const float *prev_cam, const float *prev_rgbl,
                  const RtFirstHit *prev_records, const float *rgb, const uint32_t *n,
                  const RtFirstHit *records, float *out_rgbl, float *out_box, int device);
+/* rt_clamp_run with two sphere tables: step 5 with the clamp and the "A moved
+ * sphere" step on host arrays, through the kernel that a resolve after a
+ * geometry edit runs.  prev_spheres is the table prev remembers and spheres
+ * the table now: nspheres x {cx, cy, cz, r} each, dense; both may be NULL when
+ * nspheres is 0 (every pixel is then rt_clamp_run's), a NULL table with
+ * nspheres > 0 and nspheres >= 2^32 are errors.  Any bits are legal in the
+ * tables, NaN included: the step above says what becomes of them.  Equal
+ * tables give rt_clamp_run's out_rgbl and out_box on bits.  The device reads
+ * `spheres` as an accumulator's resolve does, two float4 per sphere of which
+ * the first is {c, r}; the call fills every second one with NaN and puts one
+ * guard entry behind each table (NaN in prev's, zeros in the present one). */
+int rt_move_run(size_t width, size_t height, const RtHistoryOptions *opts,
+                const RtClampOptions *clamp, const float *prev_cam, const float *prev_rgbl,
+                const RtFirstHit *prev_records, const float *rgb, const uint32_t *n,
+                const RtFirstHit *records, float *out_rgbl, float *out_box,
+                const float *prev_spheres, const float *spheres, size_t nspheres, int device);
 
 /* Diagnostics: copies the per-sample colours (r, g, b, 0 as 4 f32) of the
  * LAST trace launch on `device` (-1 = current) to host `out` (n floats max).

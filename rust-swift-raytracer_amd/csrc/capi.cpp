@@ -719,8 +719,8 @@ int history_options(const RtHistoryOptions *opts, const char *who, RtHistoryOpti
 }
 int clamp_options(const RtClampOptions *opts, const char *who, RtClampOptions &o);
 
-// rt_history_run's and rt_clamp_run's arguments: the size, the history's options
-// -> o, the clamp's -> *c (c null: rt_history_run, none), the arrays
+// rt_history_run's, rt_clamp_run's and rt_move_run's arguments: the size, the
+// history's options -> o, the clamp's -> *c (c null: rt_history_run, none), the arrays
 int history_run_check(const char *who, size_t width, size_t height, const RtHistoryOptions *opts, RtHistoryOptions &o,
                       const RtClampOptions *clamp, RtClampOptions *c, const float *prev_cam, const float *prev_rgbl,
                       const RtFirstHit *prev_records, const float *rgb, const uint32_t *n, const RtFirstHit *records,
@@ -833,6 +833,25 @@ int rt_clamp_run(size_t width, size_t height, const RtHistoryOptions *opts, cons
         return -1;
     return rtamd::history_run(width, height, o.max_history, o.sigma_z, prev_cam, prev_rgbl, prev_records, rgb, n,
                               records, out_rgbl, device, &c, out_box);
+}
+
+int rt_move_run(size_t width, size_t height, const RtHistoryOptions *opts, const RtClampOptions *clamp,
+                const float *prev_cam, const float *prev_rgbl, const RtFirstHit *prev_records, const float *rgb,
+                const uint32_t *n, const RtFirstHit *records, float *out_rgbl, float *out_box, const float *prev_spheres,
+                const float *spheres, size_t nspheres, int device) {
+    const char *who = "rt_move_run";
+    RtHistoryOptions o;
+    RtClampOptions c;
+    if (history_run_check(who, width, height, opts, o, clamp, &c, prev_cam, prev_rgbl, prev_records, rgb, n, records,
+                          out_rgbl))
+        return -1;
+    // (any bits are legal in the tables: the contract says what the kernel does with them)
+    if ((uint64_t)nspheres >= (1ull << 32)) return rtamd::fail(who, "nspheres must be below 2^32");
+    if (nspheres && !prev_spheres) return rtamd::fail(who, "null input: prev_spheres (with nspheres > 0)");
+    if (nspheres && !spheres) return rtamd::fail(who, "null input: spheres (with nspheres > 0)");
+    const rtamd::HistoryRunMove move{prev_spheres, spheres, nspheres};
+    return rtamd::history_run(width, height, o.max_history, o.sigma_z, prev_cam, prev_rgbl, prev_records, rgb, n,
+                              records, out_rgbl, device, &c, out_box, &move);
 }
 
 int rt_device_count(void) {

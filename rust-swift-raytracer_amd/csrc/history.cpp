@@ -12,6 +12,7 @@
 // the spheres that have moved since it was made, and a resolve against it runs
 // move.hip's kernel with prev's sphere table.
 #include <algorithm>
+#include <limits>
 
 #include "runtime_internal.h"
 
@@ -226,10 +227,11 @@ int history_read_length(AccumState &a, const CameraModel &cam, float *len) {
 
 int history_run(size_t width, size_t height, float max_history, float sigma_z, const float *prev_cam,
                 const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
-                const void *records, float *out_rgbl, int device, const RtClampOptions *clamp, float *out_box) {
-    // (the arguments were checked by rt_history_run or rt_clamp_run)
+                const void *records, float *out_rgbl, int device, const RtClampOptions *clamp, float *out_box,
+                const HistoryRunMove *move) {
+    // (the arguments were checked by rt_history_run, rt_clamp_run or rt_move_run)
     int dev = -1;
-    const int rc = select_device(device, dev, clamp ? "rt_clamp_run" : "rt_history_run");
+    const int rc = select_device(device, dev, move ? "rt_move_run" : clamp ? "rt_clamp_run" : "rt_history_run");
     if (rc) return rc;
     const size_t npix = width * height;
     DevBuf<float> d_rgb;
@@ -280,7 +282,31 @@ int history_run(size_t width, size_t height, float max_history, float sigma_z, c
             c.out_box = d_box.get();
         }
     }
-    HIP_TRY(clamp ? launch_history_clamp(k, c, nullptr) : launch_history_resolve(k, nullptr));
+    // rt_move_run's tables: prev's dense, as move_table is; the present one as a
+    // device's sph_shade, {centre, r} in the first of two float4 per sphere, the
+    // second one NaN: a read that forgets the stride meets poison, not a neighbour.
+    // One guard entry stands behind each table, NaN in prev's and zeros in the
+    // present one: an index one past the end reads a sphere that moved, to nowhere,
+    // and not whatever lies behind the buffer (so the tables exist at nspheres = 0 too)
+    DevBuf<float4> d_prev_sph, d_sph;
+    HistoryMove mv{};
+    if (move) {
+        const size_t ns = move->nspheres;
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        std::vector<float4> was(ns + 1, make_float4(nan, nan, nan, nan));
+        std::vector<float4> shade(2 * (ns + 1), make_float4(nan, nan, nan, nan));
+        if (ns) std::memcpy(was.data(), move->prev_spheres, ns * sizeof(float4));
+        for (size_t i = 0; i < ns; ++i) std::memcpy(&shade[2 * i], move->spheres + 4 * i, sizeof(float4));
+        shade[2 * ns] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        HIP_TRY(d_prev_sph.grow(was.size()));
+        HIP_TRY(d_sph.grow(shade.size()));
+        HIP_TRY(hipMemcpy(d_prev_sph.get(), was.data(), was.size() * sizeof(float4), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_sph.get(), shade.data(), shade.size() * sizeof(float4), hipMemcpyHostToDevice));
+        mv = HistoryMove{d_prev_sph.get(), d_sph.get(), 2u, (uint32_t)ns};
+    }
+    HIP_TRY(move    ? launch_history_move(k, c, mv, nullptr)
+            : clamp ? launch_history_clamp(k, c, nullptr)
+                    : launch_history_resolve(k, nullptr));
     HIP_TRY(hipMemcpy(out_rgbl, d_out.get(), npix * sizeof(float4), hipMemcpyDeviceToHost));
     if (c.out_box) HIP_TRY(hipMemcpy(out_box, d_box.get(), 6 * npix * sizeof(float), hipMemcpyDeviceToHost));
     return 0;

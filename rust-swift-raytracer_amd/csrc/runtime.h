@@ -480,11 +480,16 @@ int history_reset(AccumState &a, const CameraModel &cam);
 int history_resolve(AccumState *a, const CameraModel *cam, const RtFilterOptions *filter, float *out_rgb,
                     void *out_rgba, bool on_device, hipStream_t stream, const char *who);
 int history_read_length(AccumState &a, const CameraModel &cam, float *len);
-// (run with clamp: rt_clamp_run, the clamped step 5 and, with out_box, every pixel's box)
+// (run with clamp: rt_clamp_run, the clamped step 5 and, with out_box, every pixel's box;
+// with move as well: rt_move_run, the same through the kernel that follows moved spheres)
+struct HistoryRunMove {
+    const float *prev_spheres, *spheres;  // nspheres x {centre, r}, dense host arrays
+    size_t nspheres;
+};
 int history_run(size_t width, size_t height, float max_history, float sigma_z, const float *prev_cam,
                 const float *prev_rgbl, const void *prev_records, const float *rgb, const uint32_t *n,
                 const void *records, float *out_rgbl, int device, const RtClampOptions *clamp = nullptr,
-                float *out_box = nullptr);
+                float *out_box = nullptr, const HistoryRunMove *move = nullptr);
 // The resolve's neighbourhood clamp (rt_clamp_*): the setting
 // (on false: off); it drops no snapshot.  The options were checked by the caller.
 int clamp_enable(AccumState &a, const CameraModel &cam, bool on, const RtClampOptions &o);

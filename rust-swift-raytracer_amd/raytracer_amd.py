@@ -50,7 +50,7 @@ EXPORTS = (
     "rt_history_default_options", "rt_history_enable", "rt_history_disable", "rt_history_reset",
     "rt_history_resolve", "rt_history_resolve_device", "rt_history_read_length", "rt_history_run",
     "rt_clamp_default_options", "rt_clamp_enable", "rt_clamp_disable", "rt_clamp_run",
-    "rt_world_set_sphere_geometry", "rt_device_setups",
+    "rt_world_set_sphere_geometry", "rt_device_setups", "rt_move_run",
 )
 
 
@@ -344,6 +344,10 @@ def lib(path=None):
             L.rt_world_set_sphere_geometry.argtypes = [H, C.c_size_t, fp]
             L.rt_device_setups.restype = C.c_long
             L.rt_device_setups.argtypes = [H]
+        if hasattr(L, "rt_move_run"):  # (likewise)
+            L.rt_move_run.restype = C.c_int
+            L.rt_move_run.argtypes = ([C.c_size_t, C.c_size_t, C.POINTER(HistoryOptions), C.POINTER(ClampOptions)] +
+                                      [C.c_void_p] * 10 + [C.c_size_t, C.c_int])
         _libs[path] = L
     return _libs[path]
 
@@ -988,6 +992,52 @@ def clamp_run(rgb, n, records, prev_cam=None, prev_rgbl=None, prev_records=None,
                         out_box.ctypes.data if box else None, device)
     if rc != 0:
         raise RenderError(f"rt_clamp_run failed ({rc}): {L.rt_last_error().decode()}")
+    return out, out_box
+
+
+def move_run(rgb, n, records, prev_spheres, spheres, prev_cam=None, prev_rgbl=None, prev_records=None, clamp=None,
+             box=True, device=-1, L=None, **opts):
+    """rt_move_run: rt_clamp_run through the kernel that follows moved spheres.  The
+    arrays, clamp, box and opts as clamp_run's; prev_spheres and spheres: float32[nspheres,
+    4] {cx, cy, cz, r} as prev remembers them and as they are now (None or empty: no
+    spheres) -> (rgbl, box) as clamp_run's."""
+    L = L or lib()
+    o = history_options(L, **opts)
+    co = clamp_options(L, **(clamp or {}))
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("rgb is height x width x 3 floats")
+    h, w = c.shape[:2]
+    cnt = np.ascontiguousarray(n, dtype=np.uint32)
+    g = np.ascontiguousarray(records, dtype=FIRST_HIT_DTYPE)
+    if cnt.size != w * h or g.size != w * h:
+        raise ValueError("n and records are height x width")
+    pc = pl = pg = None
+    if prev_rgbl is not None:
+        pc = np.ascontiguousarray(prev_cam, dtype=np.float32)
+        pl = np.ascontiguousarray(prev_rgbl, dtype=np.float32)
+        pg = np.ascontiguousarray(prev_records, dtype=FIRST_HIT_DTYPE)
+        if pc.size != 12 or pl.size != 4 * w * h or pg.size != w * h:
+            raise ValueError("prev_cam is 12 floats, prev_rgbl height x width x 4, prev_records height x width")
+    s0 = s1 = None
+    nsph = 0
+    if prev_spheres is not None and np.size(prev_spheres) or spheres is not None and np.size(spheres):
+        if prev_spheres is None or spheres is None:
+            raise ValueError("prev_spheres and spheres are nspheres x 4 floats each")
+        s0 = np.ascontiguousarray(prev_spheres, dtype=np.float32)
+        s1 = np.ascontiguousarray(spheres, dtype=np.float32)
+        if s0.size != s1.size or s0.size % 4:
+            raise ValueError("prev_spheres and spheres are nspheres x 4 floats each")
+        nsph = s0.size // 4
+    out = np.zeros((h, w, 4), np.float32)
+    out_box = np.zeros((h, w, 6), np.float32) if box else None
+    rc = L.rt_move_run(w, h, C.byref(o), C.byref(co),
+                       *(a.ctypes.data if a is not None else None for a in (pc, pl, pg)),
+                       c.ctypes.data, cnt.ctypes.data, g.ctypes.data, out.ctypes.data,
+                       out_box.ctypes.data if box else None,
+                       *(a.ctypes.data if a is not None else None for a in (s0, s1)), nsph, device)
+    if rc != 0:
+        raise RenderError(f"rt_move_run failed ({rc}): {L.rt_last_error().decode()}")
     return out, out_box
 
 

@@ -236,6 +236,161 @@ def test_session_with_nan_samples():
     s.close()
 
 
+# ---- 1b. the host's sparse maps: several spheres, several accumulators, the flag set late ---------
+
+def differing(s):
+    """The sphere indices whose entries differ between the table that the next resolve's
+    prev remembers and the world's table now, by the restatement's bookkeeping alone."""
+    ref = s.ref
+    cam = np.array(s.world.camera(), F).reshape(12)
+    p = ref.cur if ref.cur is not None and (ref.cur["cam"].tobytes() != cam.tobytes() or
+                                            ref.cur["edit"] != s.edit) else ref.prev
+    now = np.ascontiguousarray(s.world.spheres()[:, :4])
+    return set(np.flatnonzero((p["spheres"].view(np.uint32) != now.view(np.uint32)).any(axis=1)).tolist())
+
+
+def took_on(length, n, rec, i):
+    on = rec["prim"] == i + 1
+    return bool((length[on] > n.astype(F)[on]).any())
+
+
+@pytest.mark.parametrize("adaptive", [False, True], ids=["plain", "adaptive"])
+def test_session_with_several_moved_spheres(adaptive):
+    """Three spheres of the 60-sphere field: two moved for one resolve; a third moved and
+    the first one moved away and back to what prev remembers; one moved twice with no
+    resolve in between.  Each step's map of moved spheres is another subset."""
+    src = V.field()
+    w, h = 48, 32
+    s = MoveSession(src, w, h, adaptive, clamp=dict(gamma=1.0, radius=2, keep_on_edit=True))
+    what = f"field {'adaptive' if adaptive else 'plain'}"
+    prims, counts = np.unique(s.world.first_hit(w, h)["prim"], return_counts=True)
+    counts = np.where((prims >= 1) & (prims <= s.world.num_spheres), counts, 0)
+    a, b, c = (int(p) - 1 for p in prims[np.argsort(-counts)][:3])
+    assert np.sort(counts)[-3] >= 8, "three spheres that first_hit shows"
+    (ca, ra), (cb, rb), (cc, rc) = (MC.geometry(src, i) for i in (a, b, c))
+    d = np.array([0.03, 0.02, 0.0], F)
+    s.add(2)
+    s.resolve(f"{what}: first")
+    s.move(a, ca + d, ra)
+    s.move(b, cb - d, F(rb * F(1.125)))
+    s.add(1)
+    assert differing(s) == {a, b}
+    _, _, length, n, rec = s.resolve(f"{what}: A and B moved")
+    assert took_on(length, n, rec, a) and took_on(length, n, rec, b) and took_on(length, n, rec, c)
+    s.move(c, cc + d, rc)
+    s.move(a, ca, ra)
+    s.move(a, ca + d, ra)  # (back to the value the last resolve's snapshot remembers)
+    s.add(1)
+    assert differing(s) == {c}
+    _, _, length, n, rec = s.resolve(f"{what}: C moved, A away and back")
+    assert took_on(length, n, rec, a) and took_on(length, n, rec, c)
+    s.move(b, cb, rb)
+    s.move(b, cb + d, F(rb * F(0.875)))
+    s.add(1)
+    assert differing(s) == {b}
+    _, _, length, n, rec = s.resolve(f"{what}: B moved twice")
+    assert took_on(length, n, rec, b)
+    # all three and the camera, then nothing but the camera
+    for i, (ci, ri) in ((a, (ca, ra)), (b, (cb, rb)), (c, (cc, rc))):
+        s.move(i, ci - d, ri)
+    s.world.translate_camera(0.02, 0.0, 0.0)
+    s.add(1)
+    assert differing(s) == {a, b, c}
+    s.resolve(f"{what}: three spheres and the camera")
+    s.world.translate_camera(0.02, 0.0, 0.0)
+    s.add(1)
+    assert differing(s) == set()
+    s.resolve(f"{what}: the camera alone")
+    s.close()
+
+
+class SharedSession(MoveSession):
+    """A MoveSession on a world it shares: the edit count is the world's, kept by the test."""
+
+    def __init__(self, world, edits, w, h, clamp):
+        self.world, self._edits = world, edits
+        self.acc = world.accumulator(w, h, 64)
+        self.adaptive, self.w, self.h, self.frame = False, w, h, None
+        self.acc.history_enable()
+        self.ref = MR.MoveHistory()
+        self.clamp(**clamp)
+
+    @property
+    def edit(self):
+        return self._edits[0]
+
+    @edit.setter
+    def edit(self, v):
+        self._edits[0] = v
+
+
+@pytest.mark.parametrize("w,h", [(40, 24), (9, 9)])
+def test_two_accumulators_of_one_world(w, h):
+    """Snapshots made at different times remember different sets of moved spheres."""
+    src = scene_text("three_spheres.txt")
+    world = R.World(src)
+    edits = [0]
+    clamp = dict(gamma=1.0, radius=1, keep_on_edit=True)
+    x, y = SharedSession(world, edits, w, h, clamp), SharedSession(world, edits, w, h, clamp)
+    s1, s2 = 1, 2
+    (c1, r1), (c2, r2) = MC.geometry(src, s1), MC.geometry(src, s2)
+    d = np.array([0.05, 0.02, 0.0], F)
+    orbit(world, 0, w, h)
+    x.add(2)
+    x.resolve(f"{w}x{h} X: first")
+    x.move(s1, c1 + d, r1)
+    y.add(2)
+    y.resolve(f"{w}x{h} Y: first, after s1 moved")
+    y.move(s2, c2 - d, F(r2 * F(0.875)))
+    x.add(1)
+    y.add(1)
+    assert differing(x) == {s1, s2} and differing(y) == {s2}
+    _, _, length, n, rec = x.resolve(f"{w}x{h} X: remembers s1 and s2")
+    if (w, h) == (40, 24):
+        assert took_on(length, n, rec, s1) and took_on(length, n, rec, s2)
+    _, _, length, n, rec = y.resolve(f"{w}x{h} Y: remembers s2 alone")
+    if (w, h) == (40, 24):
+        assert took_on(length, n, rec, s1) and took_on(length, n, rec, s2)
+    x.acc.close()
+    y.move(s1, c1 + d + d, r1)
+    y.add(1)
+    assert differing(y) == {s1}
+    y.resolve(f"{w}x{h} Y: X freed, s1 moved again")
+    y.acc.close()
+    world.close()
+
+
+def test_flag_set_after_the_move():
+    """The map is kept whatever the flag says when the sphere moves: the flag counts at the resolve."""
+    w, h = 48, 32
+    src = scene_text("three_spheres.txt")
+    i, c, r = ball_of("three_spheres.txt", src)
+    d = np.array([0.05, 0.02, 0.0], F)
+    s = MoveSession(src, w, h, clamp=dict(gamma=1.0, radius=2))
+    orbit(s.world, 0, w, h)
+    s.add(2)
+    s.resolve("late flag: first, no flag")
+    s.move(i, c + d, r)
+    s.clamp(gamma=1.0, radius=2, keep_on_edit=True)
+    s.add(1)
+    assert differing(s) == {i}
+    _, _, length, n, rec = s.resolve("late flag: the flag set after the move")
+    assert took_on(length, n, rec, i)
+    # the mirror: a reset between the move and the resolve leaves no snapshot to follow from
+    s.move(i, c + d + d, r)
+    s.acc.history_reset()
+    s.ref.reset()
+    s.add(1)
+    _, px, length, n, _ = s.resolve("late flag: reset after a move")
+    assert (length == n.astype(F)).all() and px.tobytes() == s.frame.tobytes()
+    s.move(i, c + d, r)
+    s.add(1)
+    assert differing(s) == {i}
+    _, _, length, n, rec = s.resolve("late flag: the next move is followed again")
+    assert took_on(length, n, rec, i)
+    s.close()
+
+
 # ---- 2. a world without a geometry edit runs what it ran ------------------------------------
 
 def test_no_geometry_edit_is_the_clamp_restatement():

@@ -63,6 +63,13 @@ the filter's; a wait is fence.wait(stream), the host's wait fence.sync()):
   (j) history resolves on two      AccumRead::begin, for history.cpp history_resolve (a.done: the
       streams behind a pass        pass, then the first resolve's snapshots; f.done: the first
                                    resolve's staging; d->done), history_read_length (the host waits)
+  (g') geometry edits with         capi.cpp edit_begin, for rt_world_set_sphere_geometry: the
+      frames in flight             host waits on d->done before the tree and the packed spheres
+                                   change (the library waits on its own event, which a caller's
+                                   event behind it may outlast: the frames' bits are the witness)
+  (j') a geometry edit with a      the same host wait, on the d->done that AccumRead::finish recorded
+      move-path resolve in flight  behind the resolve (it reads the device's sphere array);
+                                   history.cpp upload_prev_spheres (the host waits on a.done: the pass)
 Every wait on a fence in frame.cpp, accum.cpp, filter.cpp, first_hit.cpp, history.cpp and
 serial_states.cpp is reached by a case.  Frames captured into a graph and replayed, which
 the fences do not order, are in tests/test_gpu_capture.py.
@@ -76,6 +83,8 @@ import pytest
 import clamp_ref as CR
 import filter_ref as FR
 import history_ref as HR
+import move_cases as MC
+import move_ref as MR
 import oracle as O
 import raytracer_amd as R
 import scenes as S
@@ -662,6 +671,69 @@ def test_g_material_edits_with_frames_in_flight(name):
     world.close()
 
 
+# ---- (g') geometry edits with frames in flight ------------------------------------------------------
+
+GEO_EDITS = {  # (sphere, offset from the scene file's centre, factor on its radius) before frames 1, 2, 3
+    "rtow": [(484, (0.0, 0.4, 0.0), 1.25), (485, (0.3, 0.0, 0.5), 0.75), (484, (0.0, -0.2, 0.3), 1.0)],
+    "soup": [(5, (0.2, 0.1, 0.0), 1.25), (39, (-0.2, 0.0, 0.1), 0.75), (5, (0.0, -0.1, 0.0), 1.0)],
+}
+
+
+def geo_steps(name):
+    """[(sphere, centre, radius, the scene text after this edit and those before it)]"""
+    src = text = source(name)
+    steps = []
+    for i, off, factor in GEO_EDITS[name]:
+        c, r = MC.geometry(src, i)
+        c, r = c + np.array(off, np.float32), np.float32(r * np.float32(factor))
+        text = MC.edited(text, i, c, r)
+        steps.append((i, c, r, text))
+    return steps
+
+
+def oracle_text_frame(key, text, w, h, spp, depth):
+    return memo(("oracle text", key, w, h, spp, depth),
+                lambda: O.Scene(text).render(w, h, spp, depth, mode=O.RNG_COUNTER, seed=R.DEFAULT_SEED, nthreads=NT)[0])
+
+
+@pytest.mark.parametrize("name", list(GEO_EDITS))
+def test_g_geometry_edits_with_frames_in_flight(name):
+    """Case (g) with rt_world_set_sphere_geometry: the first edit is made while the heavy
+    frame 0 runs, and the call waits for it on the host before the tree and the packed
+    spheres change; each light frame is the oracle's of the edited scene text."""
+    torch, (s,) = gpu(1)
+    w, h, spp = 96, 64, 16
+    steps = geo_steps(name)
+    want = [solo(name, w, h, A_SPP, A_DEPTH)[0]]
+    for k, (_, _, _, text) in enumerate(steps):
+        want.append(oracle_text_frame((name, k), text, w, h, spp, A_DEPTH))
+        before = want[k] if k else oracle_frame(name, w, h, spp, A_DEPTH)
+        assert (want[-1] != before).any(axis=2).sum() >= 40, f"{name}: edit {k} changes too few pixels to be seen"
+    outs = [frame_buf(torch, w, h) for _ in want]
+    world = R.World(source(name))
+    enqueue(world, w, h, outs[1], s.cuda_stream, spp, A_DEPTH)
+    torch.cuda.synchronize()
+    outs[1].zero_()
+    torch.cuda.synchronize()
+
+    enqueue(world, w, h, outs[0], s.cuda_stream, A_SPP, A_DEPTH)
+    e0 = mark(torch, s)
+    running = not e0.query()
+    events = [("frame 0", e0)]
+    for k, (i, c, r, _) in enumerate(steps, 1):
+        world.set_sphere(i, c, r)
+        enqueue(world, w, h, outs[k], s.cuda_stream, spp, A_DEPTH)
+        events.append((f"frame {k}", mark(torch, s)))
+    torch.cuda.synchronize()
+
+    assert_in_flight(running, f"{name}: the first geometry edit")
+    assert_ordered(events, f"{name}: frames after geometry edits")
+    assert_bits_equal(as_frame(outs[0], w, h), want[0], f"{name}: frame 0 against its solo render")
+    for k in range(1, len(want)):
+        assert_bits_equal(as_frame(outs[k], w, h), want[k], f"{name}: frame {k} against the oracle of the edited text")
+    world.close()
+
+
 # ---- (j) history resolves behind an accumulator's pass --------------------------------------------------
 
 @pytest.mark.parametrize("clamp", [None, dict(gamma=1.0, radius=2)], ids=["plain", "clamp"])
@@ -736,5 +808,93 @@ def test_j_history_resolves_behind_a_running_pass(clamp):
     assert as_frame(px_1, w, h).tobytes() == want_px.tobytes(), f"{what}: the resolve on sB, RGBA8"
     got = (rgb_2.cpu().numpy().reshape(h, w, 3), as_frame(px_2, w, h))
     assert_same(got, want_filtered, f"{what}: the filtered resolve on sC")
+    acc.close()
+    world.close()
+
+
+# ---- (j') a geometry edit with a move-path resolve in flight --------------------------------------------
+
+def test_j_geometry_edit_with_a_move_resolve_in_flight():
+    """A resolve that follows a moved sphere reads the device's sphere array and the
+    accumulator's table of prev's spheres.  It is enqueued on sB behind a heavy pass of
+    its accumulator (on sA) and a heavy frame of the same world (on sB); then the sphere
+    is moved again, on the host, with no wait; then add and a second resolve.  The
+    resolve's own call waits on the host for the accumulator's pass (it rewrites the
+    table's staging: history.cpp upload_prev_spheres), so what is still running when it
+    returns, and when the edit is made, is the frame in front of it on sB.
+
+    Everything expected comes from a twin world that goes through the same calls one at
+    a time, before the first enqueue: its sums, records and spheres, restated by
+    MoveHistory."""
+    torch, (sA, sB) = gpu(2)
+    w, h, hw, hh = 96, 64, A_W, A_H
+    src = source("three_spheres")
+    ball = 1
+    c, r = MC.geometry(src, ball)
+    d = np.array([0.05, 0.02, 0.0], np.float32)
+    clamp = dict(gamma=1.0, radius=2, keep_on_edit=True)
+    cap = 65536.0  # max_history
+
+    def session():
+        world = R.World(src)
+        acc = world.accumulator(w, h, A_SPP + 8, device=0)
+        acc.history_enable(max_history=cap)  # (above the pass's samples: its resolve still blends)
+        acc.clamp_enable(**clamp)
+        return world, acc
+
+    def expect():
+        world, acc = session()
+        ref = MR.MoveHistory(max_history=cap, clamp=clamp)
+        want = []
+        for edit, (k, centre) in enumerate(((2, None), (A_SPP, c + d), (1, c + d + d))):
+            if centre is not None:
+                world.set_sphere(ball, centre, r)
+            acc.add(k, stats=False)
+            rec = world.first_hit(w, h, device=0)
+            want.append(ref.resolve(acc.sums(), np.full((h, w), k, np.uint32), rec, world.camera(), edit,
+                                    world.spheres()[:, :4]))
+            if edit == 1:
+                heavy = world.render(hw, hh, A_SPP, A_DEPTH, device=0)[0]
+            if edit:
+                on = rec["prim"] == ball + 1
+                assert ref.prev["spheres"].tobytes() != world.spheres()[:, :4].tobytes()  # (the motion path)
+                assert on.sum() > 100 and (want[-1][2][on] > k).any(), "the ball takes no history: nothing to follow"
+        acc.close()
+        world.close()
+        return want, heavy
+
+    want, want_heavy = memo("j' expect", expect)
+    world, acc = session()
+    out_heavy = frame_buf(torch, hw, hh)
+    px_1, px_2 = frame_buf(torch, w, h), frame_buf(torch, w, h)
+    rgb_1, rgb_2 = (torch.zeros(h * w * 3, dtype=torch.float32, device="cuda") for _ in range(2))
+    acc.add(2, stats=False)
+    rgb_0, px_0 = acc.resolved()
+    torch.cuda.synchronize()
+
+    world.set_sphere(ball, c + d, r)
+    assert acc.add_device(A_SPP, 0, sA.cuda_stream) is None
+    e1 = mark(torch, sA)
+    enqueue(world, hw, hh, out_heavy, sB.cuda_stream, A_SPP, A_DEPTH)
+    acc.resolved_device(rgb_1.data_ptr(), px_1.data_ptr(), sB.cuda_stream)
+    e2 = mark(torch, sB)
+    running = not e2.query()
+    world.set_sphere(ball, c + d + d, r)  # (no synchronise before it: the call waits by itself)
+    assert acc.add_device(1, 0, sA.cuda_stream) is None
+    acc.resolved_device(rgb_2.data_ptr(), px_2.data_ptr(), sB.cuda_stream)
+    e3 = mark(torch, sB)
+    length = acc.history_length()
+    torch.cuda.synchronize()
+
+    what = "a geometry edit with a move-path resolve in flight"
+    assert_in_flight(running, what)
+    assert_ordered([("the heavy pass", e1), ("the first resolve", e2), ("the second resolve", e3)], what)
+    same_bits(rgb_0, want[0][0], f"{what}: the set-up's resolve")
+    assert px_0.tobytes() == want[0][1].tobytes()
+    assert_bits_equal(as_frame(out_heavy, hw, hh), want_heavy, f"{what}: the heavy frame against the twin's")
+    for k, (rgb, px) in enumerate(((rgb_1, px_1), (rgb_2, px_2)), 1):
+        same_bits(rgb.cpu().numpy().reshape(h, w, 3), want[k][0], f"{what}: resolve {k}, out_rgb")
+        assert as_frame(px, w, h).tobytes() == want[k][1].tobytes(), f"{what}: resolve {k}, RGBA8"
+    same_bits(length, want[2][2], f"{what}: history_length after the second resolve")
     acc.close()
     world.close()
